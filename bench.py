@@ -8,6 +8,11 @@ One step = the hot path over one batch of synthetic clips already resident in HB
 Weak scaling: every rank processes its own B clips; `value` is the whole-job aggregate.
 
 python bench.py --gpus N --steps K --warmup W         (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds every side measurement
+(steps from an idle GPU, per-kernel probe and rooflines, optimizer step, dead-block / reference-pitch / fp32 / x3
+lines, CPU baselines), each still subject to its own --no-... switch.  --dump-outputs DIR writes what the last
+timed step returned (loss, logits, gradients) as DIR/<name>.npy for output-for-output comparison of two builds.
 """
 from __future__ import annotations
 
@@ -41,6 +46,13 @@ def parse():
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "x3"],
                     help="bf16: the perf mode (headline); fp32: exact fp32 MFMA (parity); x3: fp32 storage with "
                          "split-bf16 GEMM products and fp32 attention (the gradient mode that follows the reference)")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements after the timed steps: steps "
+                    "from an idle GPU, the per-kernel probe and rooflines, the optimizer step, the dead-block, "
+                    "reference-pitch, fp32 and x3 lines and the CPU baselines (each has its own --no-... switch); "
+                    "without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last "
+                    "timed step returned to DIR/<name>.npy (float32): loss, logits and grads (the parameters' gradients, "
+                    "concatenated), large arrays as a fixed seeded sample of their elements (64 MB in all at most)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true", help="skip the live per-kernel event probe")
     ap.add_argument("--no-optimizer", action="store_true", help="skip timing the fused MaxFactor step")
@@ -170,6 +182,44 @@ def plumbing_line(dev, warmup=3, runs=10):
             "shape": list(out.shape)}
 
 
+DUMP_LOGITS_ELEMS = 4 << 20   # 16 MB of float32
+DUMP_GRAD_ELEMS = 8 << 20     # 32 MB of float32 over all gradients
+
+
+def dump_outputs(path, out, model):
+    """What a caller of the timed step receives from its last execution, as float32 .npy files under `path`:
+    loss.npy, logits.npy, and grads.npy -- the gradients the backward left on the parameters, concatenated in
+    named_parameters() order.  An array above its share of the budget is stored as a sample of its flattened
+    elements at sorted indices drawn from a generator seeded by the array's name and size, so two builds run
+    with the same arguments store the same elements.  Loss and logits repeat bit for bit from run to run.  The
+    gradients do not: the backward sums partials in whatever order they arrive (in bf16 mode two runs of one
+    build differ by up to 4e-3 of a parameter's largest gradient), and the analytically zero ones (the
+    depthwise-conv bias ahead of the per-sample BatchNorm) hold rounding residue only -- hence one array, to be
+    judged against the model's largest gradient like the parity tests do (tests/model_parity.py)."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+
+    def sample(name, t, cap):
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(f"{name}:{t.numel()}".encode()))
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        return t.to(torch.float32)
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+    save("loss", sample("loss", out["loss"], 1))
+    save("logits", sample("logits", out["logits"], DUMP_LOGITS_ELEMS))
+    grads = [(n, p.grad) for n, p in model.named_parameters() if p.grad is not None]
+    cap = max(1, DUMP_GRAD_ELEMS // max(len(grads), 1))
+    save("grads", torch.cat([sample("grad." + n, g, cap) for n, g in grads]))
+
+
 def free_port():
     import socket
 
@@ -198,6 +248,10 @@ def self_launch(n):
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run measures the headline only: everything that takes steps or CPU time of its own is off
+        args.no_cpu_baseline = args.no_probe = args.no_optimizer = True
+        args.no_refpitch_line = args.no_fp32_line = args.no_dead_block_line = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -264,7 +318,10 @@ def main():
     ids, labels = synth.text(B, args.text_len, cfg.tokens, seed=7 + rank)
     ids, labels = ids.to(dev), labels.to(dev)
 
-    def step():
+    dump = bool(args.dump_outputs) and rank == 0
+    last = {}  # the outputs of the last timed step, kept only where they are dumped
+
+    def step(keep=False):
         gsync.zero_grad()
         # the kernel writes (B, F, 128) (what the encoder's k3 conv consumes); the model receives the
         # reference's (B, 128, F) spectrogram as a transposed view of it, so no copy is made
@@ -273,6 +330,8 @@ def main():
                     waveform=wfeat.unsqueeze(1))
         out["loss"].backward()
         gsync.finish()
+        if keep:
+            last.update(out)
         return out["loss"]
 
     # eager launches at every N: the N = 1 point of a 1 -> 8 curve runs the same code path as N > 1, and
@@ -296,7 +355,7 @@ def main():
         # flow of the step is on device (masked MSheath, no host syncs), so the replay is the step.
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            loss = step()
+            loss = step(keep=dump)
         torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -312,7 +371,7 @@ def main():
             lib.call("asrx_set_noise_epoch", i + 1, lib.stream())
             graph.replay()
         else:
-            loss = step()
+            loss = step(keep=dump and i == args.steps - 1)
         host_s += time.perf_counter() - h0
     torch.cuda.synchronize()
     if distributed:
@@ -320,12 +379,16 @@ def main():
     elapsed = time.perf_counter() - t0
     if graph is not None:
         lib.call("asrx_set_noise_epoch", 0, lib.stream())
+    if dump:
+        # before any side measurement runs the step again and overwrites the gradients
+        dump_outputs(args.dump_outputs, last, model)
+        last.clear()
     # host_issue_ms_per_step above includes the time the host spends BLOCKED in launches once the GPU's queues are
     # full, so it approaches ms_per_step whenever the GPU is the bound too.  Issue time without that back-pressure:
     # steps started from an idle GPU (synchronised before each), the host's own time to issue one step, beside
     # that step's wall time -- issue well below wall means the step is GPU-bound (profiles/r06_host_vs_gpu.txt)
     free_issue, free_wall = [], []
-    if graph is None:
+    if graph is None and args.full:
         for _ in range(2):
             torch.cuda.synchronize()
             h0 = time.perf_counter()

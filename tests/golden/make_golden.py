@@ -40,6 +40,44 @@ def pinned_threads():
     return ctx()
 
 
+def float32_tables(store, record=False):
+    """The oracle evaluates its positional tables (oracle.model.sinusoids, rotary_freqs) in float32 like the
+    reference, through the host's vector math library, whose float32 exp / pow / log differ by an ulp between CPUs
+    and instruction sets.  An ulp of a time scale is up to 2^-17 of an angle at position 100, the toy model's hard
+    decisions amplify that, and the float64 pins below cannot absorb it -- so the tables the fixture was made with
+    are stored beside it ("table.*" keys) and replayed while it is checked.  The host's own tables are checked
+    against the stored ones here, within what float32 allows: 32 ulps of a frequency or time scale (the exp
+    argument reaches ln 10000 = 9.2, so an ulp of it moves the result by ~10), times the position for an angle.
+    record=True (making a fixture) computes the tables on this host and puts them into `store`."""
+    import contextlib
+
+    from oracle import model as om
+
+    ulps = 32 * 2.0 ** -23
+
+    def table(key, make, atol, rtol):
+        own = make()
+        if record:
+            store[key] = own.contiguous()
+        else:
+            assert torch.allclose(own, store[key], rtol=rtol, atol=atol), f"{key}: float32 table changed"
+        return store[key]
+
+    @contextlib.contextmanager
+    def ctx():
+        sinusoids, rotary_freqs = om.sinusoids, om.rotary_freqs
+        om.sinusoids = lambda n, dims, dtype, *a: table(
+            f"table.sinusoids.{n}.{dims}", lambda: sinusoids(n, dims, torch.float32, *a), n * ulps, 0.0).to(dtype)
+        om.rotary_freqs = lambda dims, head, masked: table(
+            f"table.rotary_freqs.{dims}.{head}.{int(masked)}", lambda: rotary_freqs(dims, head, masked), 0.0, ulps)
+        try:
+            yield
+        finally:
+            om.sinusoids, om.rotary_freqs = sinusoids, rotary_freqs
+
+    return ctx()
+
+
 TOY = dict(tokens=1000, mels=128, dims=128, head=2, layer=4, act="gelu", n_type="AbbyNormal")
 
 
@@ -96,7 +134,10 @@ def write_plumbing():
     from safetensors.torch import load_file
 
     audio = load_file(os.path.join(HERE, "mel_1s.safetensors"))["audio"].numpy()
-    save_file({"encoding": plumbing_encoding(audio).contiguous(), "param_checksum": param_checksum(plumbing_params())},
+    tables = {}
+    with float32_tables(tables, record=True):
+        enc = plumbing_encoding(audio).contiguous()
+    save_file({"encoding": enc, "param_checksum": param_checksum(plumbing_params()), **tables},
               os.path.join(HERE, "plumbing_1s.safetensors"))
 
 
@@ -118,8 +159,9 @@ def main():
     Pd = {k: v.double() if v.is_floating_point() else v for k, v in P.items()}
     out = {}
     for name, training in (("train", True), ("eval", False)):
-        r = om.forward(Pd, {"dims": 128, "head": 2, "layer": 4}, ids, labels, spectrogram=spec, pitch=pitch,
-                       waveform=wav, seed=7, step=3, training=training)
+        with float32_tables(out, record=True):
+            r = om.forward(Pd, {"dims": 128, "head": 2, "layer": 4}, ids, labels, spectrogram=spec, pitch=pitch,
+                           waveform=wav, seed=7, step=3, training=training)
         out[f"logits_{name}"] = r["logits"].detach()
         out[f"loss_{name}"] = r["loss"].detach().reshape(1)
     save_file({"spectrogram": spec, "pitch": pitch, "waveform": wav, "text_ids": ids, "labels": labels,

@@ -23,10 +23,12 @@ def _golden():
 def test_oracle_reproduces_plumbing_golden():
     g, m = _golden()
     assert torch.allclose(mg.param_checksum(mg.plumbing_params()), g["param_checksum"], rtol=1e-12), "init changed"
-    with mg.pinned_threads():
+    with mg.pinned_threads(), mg.float32_tables(g):
         enc = mg.plumbing_encoding(m["audio"].numpy())
     assert enc.shape == (1, 101, 256)
-    assert torch.equal(enc, g["encoding"])
+    # float64 with the fixture's own float32 tables: what is left between hosts is the summation order of the BLAS
+    # build's convolutions (K <= 768 terms, 2 layers: ~1e-13 of values up to 3.3), not a bit-for-bit property
+    assert torch.allclose(enc, g["encoding"], rtol=1e-12, atol=1e-12)
 
 
 def _hip_encoder(cuda):

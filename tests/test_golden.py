@@ -30,7 +30,7 @@ def test_oracle_reproduces_toy_model_golden():
     P = mg.toy_params()
     assert torch.allclose(mg.param_checksum(P), g["param_checksum"], rtol=1e-12), "Model init changed"
     Pd = {k: v.double() if v.is_floating_point() else v for k, v in P.items()}
-    with mg.pinned_threads():
+    with mg.pinned_threads(), mg.float32_tables(g):
         r = om.forward(Pd, {"dims": 128, "head": 2, "layer": 4}, g["text_ids"], g["labels"],
                        spectrogram=g["spectrogram"], pitch=g["pitch"], waveform=g["waveform"], seed=7, step=3,
                        training=True)

@@ -1,6 +1,6 @@
 """WER / compute_metrics (essentials.py:576-670) and the tokenizer glue (248-292): known answers, the
-oracle's literal full-matrix restatement on random word sequences, and (when the reference's
-tokenizer.json is present in this container) a decode round trip."""
+oracle's literal full-matrix restatement on random word sequences, and a decode round trip through a
+3000-id cut of the reference's tokenizer.json (tests/golden/tokenizer_3k.json)."""
 import os
 import random
 
@@ -61,10 +61,11 @@ def test_compute_metrics_cleans_and_argmaxes():
     assert metrics.clean_ids([1, 4, -100, 0, 2, 3]) == [4, 3]
 
 
-TOK = "/root/reference/tokenizer.json"
+# the reference's tokenizer.json cut down to its first 3000 ids (specials, the byte alphabet and the earliest merges;
+# merges whose parts or result fall outside are dropped), which is still a complete byte-level BPE
+TOK = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tokenizer_3k.json")
 
 
-@pytest.mark.skipif(not os.path.exists(TOK), reason="reference tokenizer.json not present")
 def test_setup_tokenizer_round_trip():
     tok = metrics.setup_tokenizer(TOK)
     assert (tok.pad_token_id, tok.bos_token_id, tok.eos_token_id) == (0, 1, 2)

@@ -15,6 +15,7 @@ if [ $what = suite ] || [ $what = all ]; then
   tail -2 gpurun_out/${T}_smoke.log
 fi
 if [ $what = bench ] || [ $what = all ]; then
-  timeout -k 10 900 python -u bench.py > gpurun_out/${T}_bench.json 2> gpurun_out/${T}_bench.err || { tail -20 gpurun_out/${T}_bench.err; exit 1; }
-  python3 -c "import json; d=json.load(open('gpurun_out/${T}_bench.json')); print(d['value'], d['ms_per_step'], {k: d[k].get('value') for k in ('fp32_workload','x3_workload','dead_block_eliminated','refpitch_workload') if k in d}, d.get('cpu_baseline',{}).get('value'))"
+  OUT=${OUT:-bench_out}; mkdir -p $OUT
+  timeout -k 10 900 python -u bench.py --full > $OUT/${T}_bench.json 2> $OUT/${T}_bench.err || { tail -20 $OUT/${T}_bench.err; exit 1; }
+  python3 -c "import json; d=json.load(open('$OUT/${T}_bench.json')); print(d['value'], d['ms_per_step'], {k: d[k].get('value') for k in ('fp32_workload','x3_workload','dead_block_eliminated','refpitch_workload') if k in d}, d.get('cpu_baseline',{}).get('value'))"
 fi

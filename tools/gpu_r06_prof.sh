@@ -5,7 +5,7 @@
 set -e
 R=$GRAFT_REPO_ROOT; T=${TAG:-r06_p}
 mkdir -p $R/gpurun_out; cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline --no-optimizer --no-dead-block-line --no-refpitch-line --no-fp32-line"
+B="$R/bench.py --full --no-cpu-baseline --no-optimizer --no-dead-block-line --no-refpitch-line --no-fp32-line"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$T -o run --output-format csv -- python3 $B --steps 5 --warmup 2 > $R/gpurun_out/prof_$T.log 2>&1
 tail -1 $R/gpurun_out/prof_$T.log | cut -c1-200
 P="$B --no-probe --steps 1 --warmup 0"

@@ -1,6 +1,6 @@
 """Launches and kernel time per headline step from a rocprofv3 kernel trace of a bench.py run (tools/gpu_r06_prof.sh):
 the trace is split at each step's log-mel tile launch, and segments FIRST .. FIRST + COUNT - 1 are averaged --
-bench.py runs W warm-up steps, K timed steps, two steps from an idle GPU and one probed step, so with the default
+bench.py --full runs W warm-up steps, K timed steps, two steps from an idle GPU and one probed step, so with the default
 --warmup 2 --steps 5 the timed steps are segments 2..6 (eager launches since round 5).
 usage: replay_step.py run_kernel_trace.csv [tag] [first=2] [count=5]"""
 import collections
