@@ -140,6 +140,9 @@ SIGNATURES = {
     "asrx_dwconv_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
     "asrx_bn_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _i32, _p]),
     "asrx_bn_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "asrx_dwconv_pre_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
+    "asrx_bn_silu_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _i32, _p]),
+    "asrx_bn_silu_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_stem1_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_stem1_bwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_embed_fwd": (_i32, [_p, _p, _p, _i64, _i64, _p]),

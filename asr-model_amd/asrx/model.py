@@ -128,16 +128,14 @@ class ConvLite(nn.Module):
         x = ops.fork(x)  # read by point1 and the residual add
         res = x
         y = ops.linear(x, self.point1.weight, self.point1.bias)  # (2D, D, 1) leaf: gradient straight into it
-        y = ops.glu(y)
-        y = ops.DWConv.apply(y, self.depth.weight, self.depth.bias)
-        if self.training:
+        y = ops.glu_dwconv(y, self.depth.weight, self.depth.bias)  # GLU's backward runs in the conv's dgrad kernel
+        if self.training:  # BatchNorm apply + SiLU in one pass each way
             stats = []
-            y = ops.BatchNormPS.apply(y, self.bn.weight, self.bn.bias, self.bn.eps, stats)
+            y = ops.batch_norm_silu(y, self.bn.weight, self.bn.bias, self.bn.eps, stats)
             self._update_running(stats[0], y.shape[1])
         else:
-            y = ops.batch_norm_eval(y, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var,
-                                    self.bn.eps)
-        y = ops.act(y, "silu")
+            y = ops.batch_norm_silu_eval(y, self.bn.weight, self.bn.bias, self.bn.running_mean,
+                                         self.bn.running_var, self.bn.eps)
         y = ops.linear(y, self.point2.weight, self.point2.bias)
         if self.training:  # res + dropout(y) in one pass
             return ops.dropout_add(res, y, sid_base, noise.key(site + ".cl"), 0.1)
@@ -197,8 +195,7 @@ class AudioEncoder(nn.Module):
             x = ops.conv3(x, layer[1])
             x = ops.layer_norm(x, layer[2].gamma, layer[2].beta, layer[2].eps)
             x = layer[3].run(x, noise, f"enc.L{l}", sid_base)
-            x = ops.act(x, "gelu")
-            x = ops.DWConv.apply(x, layer[5].weight, layer[5].bias)
+            x = ops.act_dwconv(x, "gelu", layer[5].weight, layer[5].bias)  # GELU's backward: conv's dgrad kernel
             if self.training:  # GELU -> Dropout(0.1) [-> next layer's GELU] in one kernel each way
                 fused_lead = l + 1 < n
                 x = ops.act_dropout(x, "gelu", sid_base, noise.key(f"enc.L{l}.dr"), 0.1,

@@ -1586,6 +1586,141 @@ def batch_norm_eval(x, w, b, rm, rv, eps):
     return y
 
 
+# ------------------------------------------------------------------------------- fused encoder chains
+# The encoder's convolution stack fused into its neighbours where that measured faster (bit-identical to the
+# separate ops; the removed intermediates have no other consumer): BatchNorm -> SiLU in one apply pass each
+# way, and the backward of GLU / GELU folded into the data-gradient kernel of the depthwise conv behind it.
+# FUSED_ENCODER = False routes the wrappers below through the separate ops (the comparator of
+# tests/test_gpu_encoder_fused.py); shapes the float4 kernels do not take go there too.
+FUSED_ENCODER = True
+DW_PRE = {"glu": 1, "gelu": 2}
+_DW_PRE_K = {"glu": 15, "gelu": 3}
+
+
+def _aligned(t):
+    """g handed over by autograd: contiguous and 16-byte aligned (a fresh copy when it is a view at an odd offset)."""
+    t = _c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class PreDWConv(torch.autograd.Function):
+    """pre ("glu" | "gelu"), then the depthwise conv.  The forward runs the two stand-alone kernels (pre's output
+    x feeds the conv and is kept for the weight gradient); the backward is one data-gradient launch whose epilogue
+    applies pre's backward from pre's input z ((B, T, 2C) for glu), so the conv's own data gradient is never
+    stored, plus the weight-gradient launch."""
+
+    @staticmethod
+    def forward(ctx, z, w, b, pre):
+        z = _c(z)
+        B, T = z.shape[:2]
+        C, K = w.shape[0], w.shape[-1]
+        if z.dim() != 3 or z.shape[-1] != (2 * C if pre == "glu" else C):
+            raise ValueError(f"PreDWConv({pre}): input {tuple(z.shape)} does not match {C} conv channels")
+        x = _E(B, T, C, device=z.device)
+        if pre == "glu":
+            lib.call("asrx_glu_fwd", _P(z), _P(x), B * T, C, _S())
+        else:
+            lib.call("asrx_act_fwd", _P(z), _P(x), x.numel(), ACT[pre], _S())
+        y = _E(B, T, C, device=z.device)
+        lib.call("asrx_dwconv_fwd", _P(x), _P(w), _P(b), _P(y), B, T, C, K, _S())
+        ctx.pre = pre
+        ctx.dw, ctx.db = _direct(ctx, 1, w), _direct(ctx, 2, b)
+        ctx.save_for_backward(z, x, w, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        z, x, w, b = ctx.saved_tensors
+        g = _aligned(g)
+        B, T, C = x.shape
+        K = w.shape[-1]
+        dz = _E(z.shape, device=z.device)
+        dw, db = _gbuf(w, ctx.dw), _gbuf(b, ctx.db)
+        lib.call("asrx_dwconv_pre_bwd", _P(g), _P(x), _P(z), _P(w), _P(dz), _P(dw), _P(db), B, T, C, K,
+                 DW_PRE[ctx.pre], _S())
+        return dz, _gret(w, dw, ctx.dw), _gret(b, db, ctx.db), None
+
+
+def _pre_dwconv(z, w, pre):
+    C, K = w.shape[0], w.shape[-1]
+    return (FUSED_ENCODER and K == _DW_PRE_K[pre] and C % 4 == 0 and z.numel() < 1 << 31
+            and z.data_ptr() % 16 == 0)
+
+
+def glu_dwconv(x, w, b):
+    """DWConv(GLU(x)) for x (B, T, 2C)."""
+    x = _c(x)
+    if _pre_dwconv(x, w, "glu"):
+        return PreDWConv.apply(x, w, b, "glu")
+    return DWConv.apply(glu(x), w, b)
+
+
+def act_dwconv(x, name, w, b):
+    """DWConv(act(x))."""
+    x = _c(x)
+    if name == "gelu" and _pre_dwconv(x, w, "gelu"):
+        return PreDWConv.apply(x, w, b, "gelu")
+    return DWConv.apply(act(x, name), w, b)
+
+
+class BatchNormSiLU(torch.autograd.Function):
+    """silu(BatchNormPS(x)): one statistics pass and one apply pass each way; saves x and the per-sample
+    statistics only (the BatchNorm output is recomputed in the backward)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps, stats):
+        x = _c(x)
+        B, T, C = x.shape
+        mean = _E(B, C, device=x.device)
+        rstd = _E(B, C, device=x.device)
+        y = _E(x.shape, device=x.device)
+        lib.call("asrx_bn_silu_fwd", _P(x), _P(w), _P(b), _P(y), _P(mean), _P(rstd), B, T, C, float(eps), 1, _S())
+        if stats is not None:
+            stats.append((mean, rstd))
+        ctx.dw, ctx.db = _direct(ctx, 1, w), _direct(ctx, 2, b)
+        ctx.save_for_backward(x, w, mean, rstd, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, mean, rstd, b = ctx.saved_tensors
+        g = _aligned(g)
+        B, T, C = x.shape
+        sg = _E(B, C, device=x.device)
+        sgx = _E(B, C, device=x.device)
+        dx = _E(x.shape, device=x.device)
+        dw, db = _gbuf(w, ctx.dw), _gbuf(b, ctx.db)
+        lib.call("asrx_bn_silu_bwd", _P(g), _P(x), _P(mean), _P(rstd), _P(w), _P(b), _P(sg), _P(sgx), _P(dx), _P(dw),
+                 _P(db), B, T, C, _S())
+        return dx, _gret(w, dw, ctx.dw), _gret(b, db, ctx.db), None, None
+
+
+def _bn_silu_ok(x, *ps):
+    return (FUSED_ENCODER and x.shape[-1] % 4 == 0 and x.numel() < 1 << 31
+            and all(t.data_ptr() % 16 == 0 for t in (x,) + ps))
+
+
+def batch_norm_silu(x, w, b, eps, stats):
+    """silu(BatchNormPS(x)) in train mode."""
+    x = _c(x)
+    if _bn_silu_ok(x, w, b):
+        return BatchNormSiLU.apply(x, w, b, eps, stats)
+    return act(BatchNormPS.apply(x, w, b, eps, stats), "silu")
+
+
+def batch_norm_silu_eval(x, w, b, rm, rv, eps):
+    """silu(batch_norm_eval(x)) with the running statistics, one pass."""
+    x, rm = _c(x), _c(rm)
+    if not _bn_silu_ok(x, w, b, rm):
+        return act(batch_norm_eval(x, w, b, rm, rv, eps), "silu")
+    B, T, C = x.shape
+    rstd = _E(rv.shape, device=x.device)
+    lib.call("asrx_rsqrt_eps", _P(_c(rv)), _P(rstd), rv.numel(), float(eps), _S())
+    y = _E(x.shape, device=x.device)
+    lib.call("asrx_bn_silu_fwd", _P(x), _P(w), _P(b), _P(y), _P(rm), _P(rstd), B, T, C, float(eps), 0, _S())
+    return y
+
+
 class Conv3(torch.autograd.Function):
     """k3 / padding-1 Conv1d on channels-last (B, T, Cin) -> (B, T, Cout) via implicit-im2col GEMM.
     The weight is v (Cout, Cin, 3) like nn.Conv1d, weight-normed W = g v / |v| when g is given

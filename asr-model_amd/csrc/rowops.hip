@@ -1691,13 +1691,23 @@ __global__ __launch_bounds__(256) void dwconv_bwd_w_kernel(const float* __restri
 // register each and are scattered into the R accumulators with compile-time taps, so each input
 // float4 is loaded once per tile and every x / y access is a coalesced 16-byte lane access.
 // FLIP = 1 runs the transposed conv (backward data: dx[t] = sum_k w[k] g[t - k + P]).
+//
+// PRE (FLIP only) folds the backward of the elementwise op in front of the conv (the encoder's GLU ->
+// depth k15 and GELU -> k3 chains) into the data-gradient kernel's epilogue: z is the op's input, and
+// instead of the conv's data gradient g the kernel writes the op's -- DW_PRE_GLU the 2C-wide
+// (g s | g a s (1 - s)), DW_PRE_GELU g gelu'(z) -- so g never goes through memory.  Each value is formed
+// by the expression of the stand-alone kernel (glu_bwd_kernel, act_bwd4_kernel) from the same operands:
+// bit-identical to the two kernels in sequence.
 constexpr int DW_R = 16;
+enum { DW_PRE_NONE = 0, DW_PRE_GLU = 1, DW_PRE_GELU = 2 };
 
-template <int K, bool FLIP>
+template <int K, bool FLIP, int PRE = DW_PRE_NONE>
 __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ b, float4* __restrict__ y,
-                                                          int B, int T, int C4, int ntile) {
+                                                          int B, int T, int C4, int ntile,
+                                                          const float4* __restrict__ z) {
   constexpr int P = K / 2, W = DW_R + K - 1;
+  static_assert(FLIP || PRE == DW_PRE_NONE, "PRE is an epilogue of the data-gradient form");
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (gid >= (int64_t)B * ntile * C4) return;
   const int c4 = (int)(gid % C4);
@@ -1733,10 +1743,35 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
       }
     }
   }
-  float4* ys = y + bb * T * C4 + c4;
+  if constexpr (FLIP && PRE == DW_PRE_GLU) {  // glu_bwd_kernel's two products, 2C-wide rows
+    const float4* zs = z + bb * T * 2 * C4 + c4;
+    float4* ys = y + bb * T * 2 * C4 + c4;
 #pragma unroll
-  for (int r = 0; r < DW_R; ++r)
-    if (t0 + r < T) ys[(int64_t)(t0 + r) * C4] = acc[r];
+    for (int r = 0; r < DW_R; ++r)
+      if (t0 + r < T) {
+        const int64_t o = (int64_t)(t0 + r) * 2 * C4;
+        const float4 a = zs[o], q = zs[o + C4], g = acc[r];
+        const float sx = sigmoid_f(q.x), sy = sigmoid_f(q.y), sz = sigmoid_f(q.z), sw = sigmoid_f(q.w);
+        ys[o] = make_float4(g.x * sx, g.y * sy, g.z * sz, g.w * sw);
+        ys[o + C4] = make_float4(g.x * a.x * sx * (1.f - sx), g.y * a.y * sy * (1.f - sy),
+                                 g.z * a.z * sz * (1.f - sz), g.w * a.w * sw * (1.f - sw));
+      }
+  } else if constexpr (FLIP && PRE == DW_PRE_GELU) {  // act_bwd4_kernel's product
+    const float4* zs = z + bb * T * C4 + c4;
+    float4* ys = y + bb * T * C4 + c4;
+#pragma unroll
+    for (int r = 0; r < DW_R; ++r)
+      if (t0 + r < T) {
+        const float4 v = zs[(int64_t)(t0 + r) * C4], g = acc[r];
+        ys[(int64_t)(t0 + r) * C4] =
+            make_float4(g.x * gelu_grad(v.x), g.y * gelu_grad(v.y), g.z * gelu_grad(v.z), g.w * gelu_grad(v.w));
+      }
+  } else {
+    float4* ys = y + bb * T * C4 + c4;
+#pragma unroll
+    for (int r = 0; r < DW_R; ++r)
+      if (t0 + r < T) ys[(int64_t)(t0 + r) * C4] = acc[r];
+  }
 }
 
 // Weight/bias gradient: dw[c, k] += sum_{b,t} g[b,t,c] x[b,t+k-P,c], db[c] += sum g.  A workgroup
@@ -1826,9 +1861,37 @@ static void dwconv_tiled(const float* x, const float* w, const float* b, float* 
   const int64_t threads = B * ntile * C4;
   const unsigned grid = (unsigned)((threads + 255) / 256);
   if (y) dwconv_tile_kernel<K, false><<<grid, 256, 0, stream>>>((const float4*)x, w, b, (float4*)y, (int)B, (int)T, C4,
-                                                                 ntile);
+                                                                 ntile, nullptr);
   if (dx) dwconv_tile_kernel<K, true><<<grid, 256, 0, stream>>>((const float4*)g, w, nullptr, (float4*)dx, (int)B,
-                                                                 (int)T, C4, ntile);
+                                                                 (int)T, C4, ntile, nullptr);
+  if (dw) {
+    const int nchunk = (int)((T + 8 * DW_S * DW_R - 1) / (8 * DW_S * DW_R));
+    const int64_t blocks = B * nchunk * ((C4 + 31) / 32);
+    dwconv_wgrad_kernel<K><<<(unsigned)blocks, 256, 0, stream>>>((const float4*)g, (const float4*)x, dw, db, (int)T,
+                                                                   C4, nchunk);
+  }
+}
+
+// Backward of op -> conv in two launches (PRE, see dwconv_tile_kernel): the data-gradient kernel
+// writes the gradient of the op's input z ((B, T, 2C) for DW_PRE_GLU) and the weight-gradient kernel reads
+// the conv's input x.  Fused forms exist for the two chains of the encoder, GLU -> k15 and GELU -> k3,
+// under dwconv_dispatch's float4 / alignment / 32-bit-size conditions on every tensor touched; callers
+// route anything else through the stand-alone ops.
+static bool dwconv_pre_ok(const float* g, const float* x, const float* z, const float* dz, int64_t B, int64_t T,
+                          int64_t C, int64_t K, int pre) {
+  const bool form = (pre == DW_PRE_GLU && K == 15) || (pre == DW_PRE_GELU && K == 3);
+  const uintptr_t al = (uintptr_t)g | (uintptr_t)x | (uintptr_t)z | (uintptr_t)dz;
+  return form && C % 4 == 0 && (al & 15) == 0 && B * T * C * (pre == DW_PRE_GLU ? 2 : 1) < (1LL << 31);
+}
+
+template <int K, int PRE>
+static void dwconv_pre_bwd_launch(const float* g, const float* x, const float* z, const float* w, float* dz, float* dw,
+                                  float* db, int64_t B, int64_t T, int64_t C, hipStream_t stream) {
+  const int C4 = (int)(C / 4);
+  const int ntile = (int)((T + DW_R - 1) / DW_R);
+  const int64_t threads = B * ntile * C4;
+  dwconv_tile_kernel<K, true, PRE><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+      (const float4*)g, w, nullptr, (float4*)dz, (int)B, (int)T, C4, ntile, (const float4*)z);
   if (dw) {
     const int nchunk = (int)((T + 8 * DW_S * DW_R - 1) / (8 * DW_S * DW_R));
     const int64_t blocks = B * nchunk * ((C4 + 31) / 32);
@@ -1948,12 +2011,17 @@ __global__ __launch_bounds__(1024) void bn_stats4_kernel(const float4* __restric
 }
 
 // float4 variant of the backward sums (same workgroup shape as bn_stats4_kernel).
+// SILU: g is the gradient of silu(BatchNorm(x)); the BatchNorm output is recomputed from x and the
+// statistics (bn_apply_kernel's expression) and g * silu'(.) formed in registers (act_bwd4_kernel's
+// product), then summed in the same row-group loop and order -- the same sums as on a stored product.
+template <bool SILU = false>
 __global__ __launch_bounds__(1024) void bn_bwd_stats4_kernel(const float4* __restrict__ g, const float4* __restrict__ x,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
                                                              const float* __restrict__ w, float* __restrict__ sg,
                                                              float* __restrict__ sgx, float* __restrict__ dw,
-                                                             float* __restrict__ db, int T, int C4) {
+                                                             float* __restrict__ db, int T, int C4,
+                                                             const float* __restrict__ bias) {
   __shared__ float4 sa[32][32], sx[32][32];
   const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int cchunks = (C4 + 31) / 32;
@@ -1966,8 +2034,20 @@ __global__ __launch_bounds__(1024) void bn_bwd_stats4_kernel(const float4* __res
     const float4 rs = *reinterpret_cast<const float4*>(rstd + b * 4 * C4 + 4 * c4);
     const float4* gs = g + b * T * C4 + c4;
     const float4* xs = x + b * T * C4 + c4;
+    float4 wv = make_float4(0.f, 0.f, 0.f, 0.f), bv = wv;
+    if constexpr (SILU) {
+      wv = *reinterpret_cast<const float4*>(w + 4 * c4);
+      bv = *reinterpret_cast<const float4*>(bias + 4 * c4);
+    }
     for (int t = grp; t < T; t += 32) {
-      const float4 gv = gs[(int64_t)t * C4], xv = xs[(int64_t)t * C4];
+      float4 gv = gs[(int64_t)t * C4];
+      const float4 xv = xs[(int64_t)t * C4];
+      if constexpr (SILU) {
+        gv.x = gv.x * silu_grad((xv.x - mu.x) * rs.x * wv.x + bv.x);
+        gv.y = gv.y * silu_grad((xv.y - mu.y) * rs.y * wv.y + bv.y);
+        gv.z = gv.z * silu_grad((xv.z - mu.z) * rs.z * wv.z + bv.z);
+        gv.w = gv.w * silu_grad((xv.w - mu.w) * rs.w * wv.w + bv.w);
+      }
       a.x += gv.x; a.y += gv.y; a.z += gv.z; a.w += gv.w;
       ax.x += gv.x * (xv.x - mu.x) * rs.x;
       ax.y += gv.y * (xv.y - mu.y) * rs.y;
@@ -2056,6 +2136,55 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __
     const float rs = rstd[s];
     const float xh = (x[i] - mean[s]) * rs;
     dx[i] = rs * (g[i] * w[c] - sg[s] / T - xh * sgx[s] / T);
+  }
+}
+
+// BatchNorm apply + SiLU in one pass each way (ConvLite's bn -> swish, model.py:103-104), float4 over
+// channels with 32-bit row / column arithmetic like act_dropout4_kernel.  Every value is formed by the
+// expression of bn_apply_kernel / act_fwd4_kernel / act_bwd4_kernel / bn_bwd_apply_kernel from the same
+// operands, so the results are bit-identical to the chain of stand-alone kernels; the BatchNorm output
+// is never stored.  Requires C % 4 == 0, 16-byte alignment (statistics and parameters included) and
+// n / 4 < 2^31.
+//   fwd: y = silu((x - mean) * rstd * w + bb)   (mean / rstd per sample, or shared when !per_sample: eval)
+__global__ void bn_silu_apply4_kernel(const float4* __restrict__ x, const float* __restrict__ mean,
+                                      const float* __restrict__ rstd, const float* __restrict__ w,
+                                      const float* __restrict__ bb, float4* __restrict__ y, uint32_t n4, uint32_t C4,
+                                      uint32_t T, int per_sample) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+    const uint32_t row = i / C4, c0 = (i - row * C4) * 4u;
+    const uint32_t s = per_sample ? (row / T) * (C4 * 4u) + c0 : c0;
+    const float4 v = x[i];
+    const float4 mu = *reinterpret_cast<const float4*>(mean + s), rs = *reinterpret_cast<const float4*>(rstd + s);
+    const float4 wv = *reinterpret_cast<const float4*>(w + c0), bv = *reinterpret_cast<const float4*>(bb + c0);
+    y[i] = make_float4(silu_f((v.x - mu.x) * rs.x * wv.x + bv.x), silu_f((v.y - mu.y) * rs.y * wv.y + bv.y),
+                       silu_f((v.z - mu.z) * rs.z * wv.z + bv.z), silu_f((v.w - mu.w) * rs.w * wv.w + bv.w));
+  }
+}
+
+//   bwd: gz = g * silu'(BatchNorm(x)) recomputed, then bn_bwd_apply_kernel's expression on gz
+__global__ void bn_silu_bwd_apply4_kernel(const float4* __restrict__ g, const float4* __restrict__ x,
+                                          const float* __restrict__ mean, const float* __restrict__ rstd,
+                                          const float* __restrict__ w, const float* __restrict__ bb,
+                                          const float* __restrict__ sg, const float* __restrict__ sgx,
+                                          float4* __restrict__ dx, uint32_t n4, uint32_t C4, uint32_t T) {
+  const float Tf = (float)T;
+  auto one = [&](float gv, float xv, float mu, float rs, float wc, float bc, float sgs, float sgxs)
+                 __attribute__((always_inline)) {
+    const float xh = (xv - mu) * rs;
+    const float gz = gv * silu_grad(xh * wc + bc);
+    return rs * (gz * wc - sgs / Tf - xh * sgxs / Tf);
+  };
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+    const uint32_t row = i / C4, c0 = (i - row * C4) * 4u;
+    const uint32_t s = (row / T) * (C4 * 4u) + c0;
+    const float4 gv = g[i], xv = x[i];
+    const float4 mu = *reinterpret_cast<const float4*>(mean + s), rs = *reinterpret_cast<const float4*>(rstd + s);
+    const float4 wv = *reinterpret_cast<const float4*>(w + c0), bv = *reinterpret_cast<const float4*>(bb + c0);
+    const float4 a = *reinterpret_cast<const float4*>(sg + s), ax = *reinterpret_cast<const float4*>(sgx + s);
+    dx[i] = make_float4(one(gv.x, xv.x, mu.x, rs.x, wv.x, bv.x, a.x, ax.x),
+                        one(gv.y, xv.y, mu.y, rs.y, wv.y, bv.y, a.y, ax.y),
+                        one(gv.z, xv.z, mu.z, rs.z, wv.z, bv.z, a.z, ax.z),
+                        one(gv.w, xv.w, mu.w, rs.w, wv.w, bv.w, a.w, ax.w));
   }
 }
 
@@ -2923,6 +3052,17 @@ int asrx_dwconv_bwd(const float* g, const float* x, const float* w, float* dx, f
   ASRX_LAUNCHED("asrx_dwconv_bwd");
 }
 
+int asrx_dwconv_pre_bwd(const float* g, const float* x, const float* z, const float* w, float* dz, float* dw,
+                        float* db, int64_t B, int64_t T, int64_t C, int64_t K, int pre, hipStream_t stream) {
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE(dwconv_pre_ok(g, x, z, dz, B, T, C, K, pre),
+               "asrx_dwconv_pre_bwd: GLU -> k15 or GELU -> k3 with C %% 4 == 0, 16-byte aligned tensors and "
+               "fewer than 2^31 elements");
+  if (pre == DW_PRE_GLU) dwconv_pre_bwd_launch<15, DW_PRE_GLU>(g, x, z, w, dz, dw, db, B, T, C, stream);
+  else dwconv_pre_bwd_launch<3, DW_PRE_GELU>(g, x, z, w, dz, dw, db, B, T, C, stream);
+  ASRX_LAUNCHED("asrx_dwconv_pre_bwd");
+}
+
 int asrx_bn_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd, int64_t B,
                 int64_t T, int64_t C, float eps, int use_batch_stats, hipStream_t stream) {
   if (B * T == 0) return 0;
@@ -2946,14 +3086,50 @@ int asrx_bn_bwd(const float* g, const float* x, const float* mean, const float* 
   if (C % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)mean & 15) == 0 &&
       ((uintptr_t)rstd & 15) == 0) {
     const int C4 = (int)(C / 4);
-    bn_bwd_stats4_kernel<<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>(
-        (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4);
+    bn_bwd_stats4_kernel<false><<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>(
+        (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, nullptr);
   } else {
     dim3 grid((unsigned)((C + 63) / 64), (unsigned)B);
     bn_bwd_stats_kernel<<<grid, 256, 0, stream>>>(g, x, mean, rstd, w, sg_ws, sgx_ws, dw, db, T, (int)C);
   }
   LAUNCH_EW(bn_bwd_apply_kernel, B * T * C, g, x, mean, rstd, w, sg_ws, sgx_ws, dx, B, T, (int)C);
   ASRX_LAUNCHED("asrx_bn_bwd");
+}
+
+static bool bn_silu_vec_ok(std::initializer_list<const void*> ps, int64_t B, int64_t T, int64_t C) {
+  uintptr_t al = 0;
+  for (const void* p : ps) al |= (uintptr_t)p;
+  return C % 4 == 0 && (al & 15) == 0 && B * T * C < (1LL << 31);
+}
+
+int asrx_bn_silu_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd, int64_t B,
+                     int64_t T, int64_t C, float eps, int use_batch_stats, hipStream_t stream) {
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE(bn_silu_vec_ok({x, w, b, y, mean, rstd}, B, T, C),
+               "asrx_bn_silu_fwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
+  const int C4 = (int)(C / 4);
+  if (use_batch_stats)
+    bn_stats4_kernel<<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>((const float4*)x, mean, rstd, (int)T, C4,
+                                                                           eps);
+  const int64_t n4 = B * T * C4;
+  LAUNCH_EW(bn_silu_apply4_kernel, n4, (const float4*)x, mean, rstd, w, b, (float4*)y, (uint32_t)n4, (uint32_t)C4,
+            (uint32_t)T, use_batch_stats);
+  ASRX_LAUNCHED("asrx_bn_silu_fwd");
+}
+
+int asrx_bn_silu_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
+                     const float* b, float* sg_ws, float* sgx_ws, float* dx, float* dw, float* db, int64_t B,
+                     int64_t T, int64_t C, hipStream_t stream) {
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE(bn_silu_vec_ok({g, x, mean, rstd, w, b, sg_ws, sgx_ws, dx}, B, T, C),
+               "asrx_bn_silu_bwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
+  const int C4 = (int)(C / 4);
+  bn_bwd_stats4_kernel<true><<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>(
+      (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, b);
+  const int64_t n4 = B * T * C4;
+  LAUNCH_EW(bn_silu_bwd_apply4_kernel, n4, (const float4*)g, (const float4*)x, mean, rstd, w, b, sg_ws, sgx_ws,
+            (float4*)dx, (uint32_t)n4, (uint32_t)C4, (uint32_t)T);
+  ASRX_LAUNCHED("asrx_bn_silu_bwd");
 }
 
 int asrx_stem1_fwd(const float* x, const float* W, const float* bias, float* y, int64_t B, int64_t T, int64_t D,

@@ -526,11 +526,28 @@ int asrx_dwconv_fwd(const float* x, const float* w, const float* b, float* y, in
                     int64_t K, asrx_stream_t stream);
 int asrx_dwconv_bwd(const float* g, const float* x, const float* w, float* dx, float* dw, float* db, int64_t B,
                     int64_t T, int64_t C, int64_t K, asrx_stream_t stream);
+/* Backward of op -> depthwise conv with the op's backward folded into the conv's data-gradient kernel,
+ * bit-identical to asrx_dwconv_bwd followed by the op's own backward: pre = 1 GLU -> K = 15 (ConvLite point1
+ * -> glu -> depth; z and dz are (B, T, 2C)), pre = 2 GELU -> K = 3 (encoder layer tail; z and dz are
+ * (B, T, C)).  z is the op's input, x = op(z) the conv's input (for the weight gradient); the conv's data
+ * gradient is never stored.  Requires C % 4 == 0, 16-byte aligned tensors and fewer than 2^31 elements
+ * (error otherwise: route such shapes through the separate entry points). */
+int asrx_dwconv_pre_bwd(const float* g, const float* x, const float* z, const float* w, float* dz, float* dw,
+                        float* db, int64_t B, int64_t T, int64_t C, int64_t K, int pre, asrx_stream_t stream);
 int asrx_bn_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd, int64_t B,
                 int64_t T, int64_t C, float eps, int use_batch_stats, asrx_stream_t stream);
 int asrx_bn_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w, float* sg_ws,
                 float* sgx_ws, float* dx, float* dw, float* db, int64_t B, int64_t T, int64_t C,
                 asrx_stream_t stream);
+/* silu(BatchNorm(x)) in one apply pass each way, bit-identical to asrx_bn_fwd + asrx_act_fwd and
+ * asrx_act_bwd + asrx_bn_bwd: the backward takes the gradient of the SiLU output and recomputes the
+ * BatchNorm output from x and the statistics.  Same float4 requirements as asrx_dwconv_pre_bwd, on the
+ * statistics, parameters and workspaces too. */
+int asrx_bn_silu_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd, int64_t B,
+                     int64_t T, int64_t C, float eps, int use_batch_stats, asrx_stream_t stream);
+int asrx_bn_silu_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
+                     const float* b, float* sg_ws, float* sgx_ws, float* dx, float* dw, float* db, int64_t B,
+                     int64_t T, int64_t C, asrx_stream_t stream);
 int asrx_stem1_fwd(const float* x, const float* W, const float* bias, float* y, int64_t B, int64_t T, int64_t D,
                    asrx_stream_t stream);
 int asrx_stem1_bwd(const float* g, const float* x, float* dW, float* db, int64_t B, int64_t T, int64_t D,
