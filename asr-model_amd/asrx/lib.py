@@ -183,6 +183,9 @@ SIGNATURES = {
     "asrx_wave_pool": (_i32, [_p, _i64, _i64, _i64, _i64, _p, _p]),
     "asrx_maxfactor_param_bytes": (_i32, []),
     "asrx_maxfactor_step": (_i32, [_p, _i32, _i64, _i64, _i64, _i64, _i64, _p, _p]),
+    "asrx_maxfactor_step_ex": (_i32, [_p, _i32, _i64, _i64, _i64, _i64, _i64, _p, _p, _i32, _p]),
+    "asrx_grad_stats_param_bytes": (_i32, []),
+    "asrx_grad_stats": (_i32, [_p, _i32, _i64, _f32, _f32, _f32, _p, _p, _p]),
     "asrx_abby_record_cond": (_i32, [_p]),
     "asrx_gemm_wn_ce": (_i32, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p]),
     "asrx_gemm_wn_ce_f32": (_i32, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p]),

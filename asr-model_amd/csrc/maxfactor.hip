@@ -20,6 +20,9 @@
 // split into 64 / gsz lane groups of gsz = pow2 >= row length (<= 64) lanes, one row per group:
 // the k3 conv weights are 2*D*D rows of 3 (a row per wave ran 3 of 64 lanes and made the step ~30x
 // slower than its HBM bytes; now 16 rows share a wave).
+// asrx_maxfactor_step_ex runs the same step under a device control word (gradient scale, skip flag:
+// csrc/gradstats.hip writes it) and with the per-parameter update-RMS cap of optimizerc.py:121-128:
+//   update_rms = ||step dir|| / sqrt(n);  if update_rms > cap ||p|| / sqrt(n): step *= that / (update_rms + 1e-8)
 #include "common.h"
 
 namespace asrx {
@@ -32,7 +35,7 @@ struct MFParam {
   float* v;   // v [n]                   (vectors)
   int64_t n;
   int mats, rows, cols;
-  int mode;  // 0 vector (max), 1 matrix + max, 2 matrix + median
+  int mode;  // bits 0-1: 0 vector (max), 1 matrix + max, 2 matrix + median; MF_CLIP: cap the update RMS
   float beta, rho, lr, decay, gamma, d, eps1, eps2;
   int64_t row0;  // offset of this parameter's rows in the flat row space (mats * rows, or 1)
   int64_t cc0;   // offset in the flat (mat, col, row-chunk) space of the column kernel
@@ -40,8 +43,16 @@ struct MFParam {
   int64_t mat0;  // offset in the flat mat space
   int64_t item0; // offset in the flat wave-work-item space of the row kernels
   int gsz;       // lanes per row (power of two <= 64); 64 / gsz rows per work item
-  int pad_;
+  float cap;     // update-RMS cap relative to the parameter RMS (MF_CLIP); 0 in records without it
 };
+
+constexpr int MF_CLIP = 4;  // mode flag: optimizerc.py:121-128 (group["clip"])
+
+// Control word of asrx_maxfactor_step_ex (asrx_grad_stats writes it): ctl[0] scales every gradient
+// read, ctl[1] != 0 skips the step -- every kernel returns before it writes anything.  Without a
+// control word the scale is 1 (g * 1.f is exact: the plain step's results are unchanged).
+__device__ __forceinline__ bool mf_skip(const float* ctl) { return ctl != nullptr && ctl[1] != 0.f; }
+__device__ __forceinline__ float mf_gscale(const float* ctl) { return ctl != nullptr ? ctl[0] : 1.f; }
 
 constexpr int MF_CHUNK = 256;  // rows per column-sum work item
 
@@ -77,7 +88,7 @@ __device__ __forceinline__ void mf_for_rows(const MFParam* __restrict__ tab, int
       else hi = mid - 1;
     }
     const int G = tab[lo].gsz;
-    const int64_t nr = tab[lo].mode == 0 ? 1 : (int64_t)tab[lo].mats * tab[lo].rows;
+    const int64_t nr = (tab[lo].mode & 3) == 0 ? 1 : (int64_t)tab[lo].mats * tab[lo].rows;
     const int64_t lr_ = (it - offs[lo]) * (64 / G) + lane / G;
     body(tab[lo].row0 + lr_, lo, lr_ < nr, lane & (G - 1), G);
   }
@@ -99,16 +110,19 @@ __device__ __forceinline__ float* pstats(float* stats, int i) { return stats + 4
 // ---- K1: row sums of g^2 -> row_var (matrices) or v (vectors); per-row sum of p^2 (reduced per
 // parameter by K1b -- same-address atomics from thousands of rows would serialise)
 __global__ __launch_bounds__(256) void mf_rows_kernel(const MFParam* __restrict__ tab, int np, int64_t nitems,
-                                                      float* __restrict__ row_p2) {
+                                                      float* __restrict__ row_p2, const float* __restrict__ ctl) {
+  if (mf_skip(ctl)) return;
+  const float gs = mf_gscale(ctl);
   mf_for_rows(tab, np, nitems, [&](int64_t row, int i, bool ok, int sub, int G) {
-    const MFParam P = tab[i];
+    MFParam P = tab[i];
+    P.mode &= 3;
     const int64_t lr_ = row - P.row0;
     const int64_t base = P.mode == 0 ? 0 : lr_ * P.cols;
     const int len = ok ? (P.mode == 0 ? (int)P.n : P.cols) : 0;
     float sg = 0.f, sp = 0.f;
 #pragma unroll 8
     for (int c = sub; c < len; c += G) {
-      const float g = P.g[base + c], w = P.p[base + c];
+      const float g = gs * P.g[base + c], w = P.p[base + c];
       sg += g * g;
       sp += w * w;
       if (P.mode == 0) P.v[c] = P.gamma * P.v[c] + (1.f - P.gamma) * g * g;
@@ -131,10 +145,14 @@ __global__ __launch_bounds__(256) void mf_rows_kernel(const MFParam* __restrict_
 __global__ __launch_bounds__(256) void mf_param_reduce_kernel(const MFParam* __restrict__ tab, int np, int pass,
                                                               const float* __restrict__ ra,
                                                               const float* __restrict__ rb, float* __restrict__ stats,
-                                                              float* __restrict__ mrv) {
+                                                              float* __restrict__ mrv, const float* __restrict__ rc,
+                                                              const float* __restrict__ ctl) {
+  if (mf_skip(ctl)) return;
   __shared__ float red[8];
   const int i = blockIdx.x;
-  const MFParam P = tab[i];
+  MFParam P = tab[i];
+  const bool clip = (P.mode & MF_CLIP) != 0 && rc != nullptr;
+  P.mode &= 3;
   const int64_t nr = P.mode == 0 ? 1 : (int64_t)P.mats * P.rows;
   float s = 0.f, mx = 0.f;
   for (int64_t r = threadIdx.x; r < nr; r += 256) {
@@ -143,6 +161,13 @@ __global__ __launch_bounds__(256) void mf_param_reduce_kernel(const MFParam* __r
   }
   s = block_sum<256>(s, red);
   __syncthreads();
+  if (pass == 1 && clip) {  // stats[3] = sum over rows of count(u != 0) rowred^2 (block-uniform branch)
+    float sc = 0.f;
+    for (int64_t r = threadIdx.x; r < nr; r += 256) sc += rc[P.row0 + r];
+    sc = block_sum<256>(sc, red);
+    __syncthreads();
+    if (threadIdx.x == 0) stats[4 * i + 3] = sc;
+  }
   if (pass == 1) {
     mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
@@ -166,12 +191,14 @@ __global__ __launch_bounds__(256) void mf_param_reduce_kernel(const MFParam* __r
 
 // ---- K2: column sums of g^2 over chunks of MF_CHUNK rows (atomics into colacc)
 __global__ __launch_bounds__(256) void mf_cols_kernel(const MFParam* __restrict__ tab, int np, int64_t ncc,
-                                                      float* __restrict__ colacc) {
+                                                      float* __restrict__ colacc, const float* __restrict__ ctl) {
+  if (mf_skip(ctl)) return;
+  const float gs = mf_gscale(ctl);
   const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (w >= ncc) return;
   const int i = find_param(tab, np, w, 1);
   const MFParam P = tab[i];
-  if (P.mode == 0) return;
+  if ((P.mode & 3) == 0) return;
   const int64_t q = w - P.cc0;
   const int nch = (P.rows + MF_CHUNK - 1) / MF_CHUNK;
   const int col = (int)(q % P.cols);
@@ -181,7 +208,7 @@ __global__ __launch_bounds__(256) void mf_cols_kernel(const MFParam* __restrict_
   const float* g = P.g + (int64_t)m * P.rows * P.cols + col;
   float s = 0.f;
   for (int r = r0; r < r1; ++r) {
-    const float x = g[(int64_t)r * P.cols];
+    const float x = gs * g[(int64_t)r * P.cols];
     s += x * x;
   }
   atomicAdd(colacc + P.col0 + (int64_t)m * P.cols + col, s);
@@ -189,12 +216,14 @@ __global__ __launch_bounds__(256) void mf_cols_kernel(const MFParam* __restrict_
 
 // ---- K3: col_var lerp (one thread per (param, mat, col))
 __global__ __launch_bounds__(256) void mf_colfin_kernel(const MFParam* __restrict__ tab, int np, int64_t ncols,
-                                                        const float* __restrict__ colacc) {
+                                                        const float* __restrict__ colacc,
+                                                        const float* __restrict__ ctl) {
+  if (mf_skip(ctl)) return;
   const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (w >= ncols) return;
   const int i = find_param(tab, np, w, 2);
   const MFParam P = tab[i];
-  if (P.mode == 0) return;
+  if ((P.mode & 3) == 0) return;
   const int64_t q = w - P.col0;
   const float mean = colacc[w] / ((float)P.rows + 1e-8f);
   const float old = P.cv[q];
@@ -211,9 +240,14 @@ __device__ __forceinline__ float mf_u(const MFParam& P, float g, float rvi, floa
 // ---- K4: per row: u, row max |u| (or median |u|), and the parameter's sum u^2 / max |u|
 __global__ __launch_bounds__(256) void mf_ustats_kernel(const MFParam* __restrict__ tab, int np, int64_t nitems,
                                                         const float* __restrict__ mrv, float* __restrict__ rowred,
-                                                        float* __restrict__ row_u2, float* __restrict__ row_umax) {
+                                                        float* __restrict__ row_u2, float* __restrict__ row_umax,
+                                                        float* __restrict__ row_c, const float* __restrict__ ctl) {
+  if (mf_skip(ctl)) return;
+  const float gs = mf_gscale(ctl);
   mf_for_rows(tab, np, nitems, [&](int64_t row, int i, bool ok, int sub, int G) {
-    const MFParam P = tab[i];
+    MFParam P = tab[i];
+    const bool clip = (P.mode & MF_CLIP) != 0 && row_c != nullptr;
+    P.mode &= 3;
     const int64_t lr_ = ok ? row - P.row0 : 0;
     const int len = ok ? (P.mode == 0 ? (int)P.n : P.cols) : 0;
     const int64_t base = P.mode == 0 ? 0 : lr_ * P.cols;
@@ -221,16 +255,18 @@ __global__ __launch_bounds__(256) void mf_ustats_kernel(const MFParam* __restric
     const float rvi = P.mode == 0 ? 0.f : P.rv[lr_];
     const float mr = P.mode == 0 ? 0.f : mrv[P.mat0 + m];
     const float* cvr = P.mode == 0 ? P.v : P.cv + (int64_t)m * P.cols;
-    auto u_at = [&](int c) { return mf_u(P, P.g[base + c], P.mode == 0 ? cvr[c] : rvi, cvr[c], mr); };
-    float su = 0.f, mx = 0.f;
+    auto u_at = [&](int c) { return mf_u(P, gs * P.g[base + c], P.mode == 0 ? cvr[c] : rvi, cvr[c], mr); };
+    float su = 0.f, mx = 0.f, nz = 0.f;
 #pragma unroll 8
     for (int c = sub; c < len; c += G) {
       const float u = u_at(c);
       su += u * u;
       mx = fmaxf(mx, fabsf(u));
+      nz += u != 0.f ? 1.f : 0.f;  // elements whose sign(u) row_scale is nonzero
     }
     su = grp_sum(su, G);
     mx = grp_max(mx, G);
+    if (clip) nz = grp_sum(nz, G);  // uniform over the wave's groups of one parameter; all lanes shuffle
     float red = mx;
     if (P.mode == 2) {
       // lower median of |u| over the row (torch.median): MSB-first radix select on the float bits
@@ -256,6 +292,7 @@ __global__ __launch_bounds__(256) void mf_ustats_kernel(const MFParam* __restric
       rowred[row] = red;
       row_u2[row] = su;
       row_umax[row] = mx;
+      if (clip) row_c[row] = nz * red * red;
     }
   });
 }
@@ -263,10 +300,15 @@ __global__ __launch_bounds__(256) void mf_ustats_kernel(const MFParam* __restric
 // ---- K5: apply
 __global__ __launch_bounds__(256) void mf_apply_kernel(const MFParam* __restrict__ tab, int np, int64_t nitems,
                                                        const float* __restrict__ mrv, const float* __restrict__ rowred,
-                                                       const float* __restrict__ stats) {
+                                                       const float* __restrict__ stats, const float* __restrict__ ctl,
+                                                       int clip_any) {
+  if (mf_skip(ctl)) return;
+  const float gs = mf_gscale(ctl);
   mf_for_rows(tab, np, nitems, [&](int64_t row, int i, bool ok, int sub, int G) {
     if (!ok) return;  // no group-wide shuffles below
-    const MFParam P = tab[i];
+    MFParam P = tab[i];
+    const bool clip = (P.mode & MF_CLIP) != 0 && clip_any != 0;  // stats[3] exists only with clip_any
+    P.mode &= 3;
     const int64_t lr_ = row - P.row0;
     const int len = P.mode == 0 ? (int)P.n : P.cols;
     const int64_t base = P.mode == 0 ? 0 : lr_ * P.cols;
@@ -280,12 +322,17 @@ __global__ __launch_bounds__(256) void mf_apply_kernel(const MFParam* __restrict
     const float div = inf > 0.f ? fmaxf(inf, P.eps1) : 1.f;  // update /= max(inf, eps1) when inf > 0
     const float denom = fmaxf(1.f, sqrtf(st[1]) / div / (sqrtf(n) * P.d));
     const float scale = rowred[row] / div;
-    const float step = alpha / denom;
+    float step = alpha / denom;
     const float keep = 1.f - P.lr * P.decay;
+    if (clip) {  // optimizerc.py:121-128; norm(param) there is taken after the decay multiply (:78)
+      const float update_rms = step * sqrtf(st[3]) / div / sqrtf(n);
+      const float max_allowed = keep * sqrtf(st[0] / n) * P.cap;
+      if (update_rms > max_allowed) step *= max_allowed / (update_rms + 1e-8f);
+    }
     const float* cvr = P.mode == 0 ? P.v : P.cv + (int64_t)m * P.cols;
 #pragma unroll 8
     for (int c = sub; c < len; c += G) {
-      const float u = mf_u(P, P.g[base + c], P.mode == 0 ? cvr[c] : rvi, cvr[c], mr);
+      const float u = mf_u(P, gs * P.g[base + c], P.mode == 0 ? cvr[c] : rvi, cvr[c], mr);
       const float sgn = u > 0.f ? 1.f : (u < 0.f ? -1.f : 0.f);
       P.p[base + c] = P.p[base + c] * keep - step * sgn * scale;
       // optimizerc.py:89-97 updates var_est in place, and for a vector var_est IS state["v"]: the
@@ -302,9 +349,11 @@ using namespace asrx;
 extern "C" int asrx_maxfactor_param_bytes(void) { return (int)sizeof(MFParam); }
 
 // table: device array of np MFParam (asrx/optim.py packs it); ws: float workspace of
-// 4 np + 4 nrows + ncols + nmats floats; ncc = size of the (mat, col, row-chunk) space.
-extern "C" int asrx_maxfactor_step(const void* table, int np, int64_t nrows, int64_t ncols, int64_t ncc,
-                                   int64_t nmats, int64_t nitems, float* ws, hipStream_t stream) {
+// 4 np + 4 nrows + ncols + nmats floats (+ nrows more, at the end, when clip_any is set);
+// ncc = size of the (mat, col, row-chunk) space.  ctl: null, or the control word of asrx_grad_stats.
+extern "C" int asrx_maxfactor_step_ex(const void* table, int np, int64_t nrows, int64_t ncols, int64_t ncc,
+                                      int64_t nmats, int64_t nitems, float* ws, const float* ctl, int clip_any,
+                                      hipStream_t stream) {
   ASRX_REQUIRE(np > 0, "asrx_maxfactor_step: no parameters");
   const MFParam* tab = reinterpret_cast<const MFParam*>(table);
   float* stats = ws;
@@ -313,18 +362,24 @@ extern "C" int asrx_maxfactor_step(const void* table, int np, int64_t nrows, int
   float* row_b = row_a + nrows;   // max |u| per row
   float* colacc = row_b + nrows;
   float* mrv = colacc + ncols;
+  float* row_c = clip_any ? mrv + nmats : nullptr;  // count(u != 0) rowred^2 per row
   if (ncols > 0) (void)hipMemsetAsync(colacc, 0, sizeof(float) * ncols, stream);
   ASRX_REQUIRE(np <= MF_MAXP, "asrx_maxfactor_step: at most %d parameters per call", MF_MAXP);
   ASRX_REQUIRE(nitems > 0 && nitems <= nrows, "asrx_maxfactor_step: bad work-item count %ld", (long)nitems);
   const unsigned gr = (unsigned)std::min<int64_t>((nitems + 3) / 4, 4096);
-  mf_rows_kernel<<<gr, 256, 0, stream>>>(tab, np, nitems, row_a);
-  mf_param_reduce_kernel<<<np, 256, 0, stream>>>(tab, np, 0, row_a, nullptr, stats, mrv);
+  mf_rows_kernel<<<gr, 256, 0, stream>>>(tab, np, nitems, row_a, ctl);
+  mf_param_reduce_kernel<<<np, 256, 0, stream>>>(tab, np, 0, row_a, nullptr, stats, mrv, nullptr, ctl);
   if (ncc > 0) {
-    mf_cols_kernel<<<(unsigned)((ncc + 255) / 256), 256, 0, stream>>>(tab, np, ncc, colacc);
-    mf_colfin_kernel<<<(unsigned)((ncols + 255) / 256), 256, 0, stream>>>(tab, np, ncols, colacc);
+    mf_cols_kernel<<<(unsigned)((ncc + 255) / 256), 256, 0, stream>>>(tab, np, ncc, colacc, ctl);
+    mf_colfin_kernel<<<(unsigned)((ncols + 255) / 256), 256, 0, stream>>>(tab, np, ncols, colacc, ctl);
   }
-  mf_ustats_kernel<<<gr, 256, 0, stream>>>(tab, np, nitems, mrv, rowred, row_a, row_b);
-  mf_param_reduce_kernel<<<np, 256, 0, stream>>>(tab, np, 1, row_a, row_b, stats, mrv);
-  mf_apply_kernel<<<gr, 256, 0, stream>>>(tab, np, nitems, mrv, rowred, stats);
+  mf_ustats_kernel<<<gr, 256, 0, stream>>>(tab, np, nitems, mrv, rowred, row_a, row_b, row_c, ctl);
+  mf_param_reduce_kernel<<<np, 256, 0, stream>>>(tab, np, 1, row_a, row_b, stats, mrv, row_c, ctl);
+  mf_apply_kernel<<<gr, 256, 0, stream>>>(tab, np, nitems, mrv, rowred, stats, ctl, clip_any);
   ASRX_LAUNCHED("asrx_maxfactor_step");
+}
+
+extern "C" int asrx_maxfactor_step(const void* table, int np, int64_t nrows, int64_t ncols, int64_t ncc,
+                                   int64_t nmats, int64_t nitems, float* ws, hipStream_t stream) {
+  return asrx_maxfactor_step_ex(table, np, nrows, ncols, ncc, nmats, nitems, ws, nullptr, 0, stream);
 }

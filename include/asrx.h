@@ -571,6 +571,28 @@ int asrx_ce_bwd(const float* z, const int64_t* labels, const float* lse, const f
 int asrx_maxfactor_param_bytes(void);
 int asrx_maxfactor_step(const void* table, int np, int64_t nrows, int64_t ncols, int64_t ncc, int64_t nmats,
                         int64_t nitems, float* ws, asrx_stream_t stream);
+/* The same step under a device control word (ctl[0]: every gradient read becomes ctl[0] * g; ctl[1] != 0:
+ * the step is skipped, every kernel returns before it writes, parameters and state stay bit-identical), and
+ * with the per-parameter update-RMS cap of optimizerc.py:121-128 for records whose mode carries the clip
+ * flag (bit 2; the cap is the record's last float).  ctl may be null (scale 1, no skip); clip_any != 0 says
+ * some record carries the flag, and ws then holds nrows more floats (4 np + 5 nrows + ncols + nmats).
+ * asrx_maxfactor_step is this call with ctl = null, clip_any = 0. */
+int asrx_maxfactor_step_ex(const void* table, int np, int64_t nrows, int64_t ncols, int64_t ncc, int64_t nmats,
+                           int64_t nitems, float* ws, const float* ctl, int clip_any, asrx_stream_t stream);
+
+/* ---- gradient statistics between backward and the optimizer step (essentials.py:778-821: per-parameter
+ *      norms, global norm, the inf/NaN check of GradScaler.unscale_, clip_grad_norm_) over every gradient in
+ *      two launches, no host sync, no atomics (two calls on one input give bit-identical output).
+ *      table: device array of np records {const float* g; int64 n; int64 item0} (size from
+ *      asrx_grad_stats_param_bytes(); item0 = offset of the gradient's first 4096-element chunk in the flat
+ *      chunk space, nitems = their total; np <= 4096); gradients need 4-byte alignment only.
+ *      stats[np + 4]: stats[i] = sum (inv_scale g_i)^2, then the control word ctl = stats + np:
+ *      ctl[0] = inv_scale * min(1, max_norm / (total_norm + eps)) (inv_scale when max_norm <= 0, 0 when
+ *      found_inf), ctl[1] = found_inf (a NaN / inf element, or a total norm that is not finite),
+ *      ctl[2] = total_norm, ctl[3] = number of non-finite elements.  ws: 2 nitems floats. ------------------- */
+int asrx_grad_stats_param_bytes(void);
+int asrx_grad_stats(const void* table, int np, int64_t nitems, float inv_scale, float max_norm, float eps,
+                    float* stats, float* ws, asrx_stream_t stream);
 
 
 /* ---- step glue (csrc/stepops.hip): ops that ran as stock ATen kernels on the hot path ------------
