@@ -426,6 +426,24 @@ FUSED_BIAS_GRAD = True
 BIAS_CHECK = None
 
 
+def _staged_f32_dy(A, lda, x2, M, K, rows):
+    """Where _wgrad sends an fp32 dY: 1 the register-staged kernel with a bf16-stored X, 0 the same kernel with an
+    fp32 X, None neither (a copy of X to fp32, or the split-K LDS-DMA kernel).  wgrad_cols2 asks the same question."""
+    if is_bf16(x2):
+        return None if (M % 4 or K % 8 or lda % 4 or x2.stride(0) != K or A.data_ptr() % 16) else 1
+    tiles = ((M + 127) // 128) * ((K + 127) // 128)
+    ok4 = M % 4 == 0 and K % 4 == 0 and lda % 4 == 0 and A.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0
+    # register-staged bf16 kernel with transpose reads (csrc/gemm_wg.hip): faster where the output
+    # has few tiles (D x D weights, 1.2-2.6x on the 8192-row text side); the wide 1152/1536 outputs at
+    # 192k rows stay on the split-K LDS-DMA kernel (5-12 % faster there, tools/wgrad_bench.py); at 24-48k rows
+    # (small / medium B=8) every output up to 72 tiles is 5-25 % faster on the staged kernel, 768 x 3072 is not
+    # (profiles/r06_wgrad_bench.txt)
+    if prec.get() == prec.PREC_BF16 and ok4 and x2.stride(0) == K and (tiles <= 9 or rows <= 16384
+                                                                        or (rows <= 50000 and tiles <= 72)):
+        return 0
+    return None
+
+
 def _wgrad(A, lda, x2, out, M, K, rows, db=None):
     """out (M, K) += A^T x2 over `rows` rows (A: (rows, >= M) with row stride lda, x2: (rows, K), fp32 or
     bf16-stored); db (M,): += the column sums of A (the bias gradient) -- in the same kernel pass on the
@@ -478,18 +496,11 @@ def _wgrad(A, lda, x2, out, M, K, rows, db=None):
             return staged(1, int(xb), "asrx_wgrad_bf16_ab", 2 + int(xb))
     if is_bf16(x2):
         # a bf16-stored activation: the register-staged bf16 kernel at every shape (its X bytes halve)
-        if M % 4 or K % 8 or lda % 4 or x2.stride(0) != K or A.data_ptr() % 16:
+        if _staged_f32_dy(A, lda, x2, M, K, rows) != 1:
             x2 = x2.float()
         else:
             return staged(0, 1, "asrx_wgrad_bf16_ex", 1)
-    ok4 = M % 4 == 0 and K % 4 == 0 and lda % 4 == 0 and A.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0
-    # register-staged bf16 kernel with transpose reads (csrc/gemm_wg.hip): faster where the output
-    # has few tiles (D x D weights, 1.2-2.6x on the 8192-row text side); the wide 1152/1536 outputs at
-    # 192k rows stay on the split-K LDS-DMA kernel (5-12 % faster there, tools/wgrad_bench.py); at 24-48k rows
-    # (small / medium B=8) every output up to 72 tiles is 5-25 % faster on the staged kernel, 768 x 3072 is not
-    # (profiles/r06_wgrad_bench.txt)
-    if prec.get() == prec.PREC_BF16 and ok4 and x2.stride(0) == K and (tiles <= 9 or rows <= 16384
-                                                                        or (rows <= 50000 and tiles <= 72)):
+    if _staged_f32_dy(A, lda, x2, M, K, rows) == 0:
         return staged(0, 0, "asrx_wgrad_bf16")
     gemm(A, x2, out, M=M, N=K, K=rows, lda=lda, ldb=K, ldc=K, a_kc=False, b_kc=False, beta=1.0, splitk=sk)
     if db is not None:
@@ -502,6 +513,29 @@ def wgrad_cols(dy, c0, n, x, out):
     gradient of one column block of a GEMM output, read in place (no copy of the block)."""
     rows, ld = dy.shape
     return _wgrad(dy[:, c0:], ld, x, out, n, x.shape[1], rows)
+
+
+def wgrad_cols2(dy, n0, out0, out1, x):
+    """out0 (n0, K) += dy[:, :n0]^T @ x and out1 (n - n0, K) += dy[:, n0:]^T @ x in ONE pass over dy and x
+    (asrx_wgrad_split: the two column blocks are one product with two destinations) where both blocks would
+    take the register-staged bf16 kernel with an fp32 x (_staged_f32_dy; the case measured); two
+    wgrad_cols calls otherwise (parity modes, unaligned shapes, a bf16-stored dy or x)."""
+    rows, n = dy.shape
+    K = x.shape[1]
+    n1 = n - n0
+    if not (0 < n0 < n and n0 % 4 == 0 and out0.stride(1) == 1 and out1.stride(1) == 1
+            and not is_bf16(dy) and _staged_f32_dy(dy, n, x, n0, K, rows) == 0
+            and _staged_f32_dy(dy[:, n0:], n, x, n1, K, rows) == 0):
+        wgrad_cols(dy, 0, n0, x, out0)
+        return wgrad_cols(dy, n0, n1, x, out1)
+    lib.require_gpu(dy, x, out0, out1)
+    tiles = ((n + 127) // 128) * ((K + 127) // 128)
+    sk = _splitk_for(rows, tiles)
+    e0 = probe.begin("gemm")
+    lib.call("asrx_wgrad_split", lib.ptr(dy), n, lib.ptr(x), 0, K, lib.ptr(out0), out0.stride(0),
+             lib.ptr(out1), out1.stride(0), n0, n, K, rows, sk, lib.stream())
+    probe.end("gemm", e0, 2.0 * n * K * rows, ("wgrad", n, K, rows, sk, "split"))
+    return out1
 
 
 def linear_wgrad(dy, x, out=None, accumulate=False, db=None):

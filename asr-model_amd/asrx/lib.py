@@ -80,6 +80,8 @@ SIGNATURES = {
     "asrx_vgate_weights": (_i32, [_p] * 7 + [_i64, _i64, _i64, _p]),
     "asrx_msheath_row_fwd": (_i32, [_p] * 6 + [_i64] + [_p] * 14 + [_i64] * 4 + [_f32, _f32, _p, _i64, _i64, _p]),
     "asrx_msheath_row_bwd": (_i32, [_p] * 11 + [_i64] + [_p] * 18 + [_i64] * 4 + [_f32, _p, _i64, _i64, _p]),
+    "asrx_msheath_row_bwd2": (_i32, [_i32, _p, _p, _p, _f32, _p] + [_p] * 11 + [_i64] + [_p] * 18 + [_i64] * 4
+                              + [_f32, _p, _i64, _i64, _p]),
     "asrx_gemm_wn_rows": (_i32, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _f32, _f32, _i32, _i32, _p,
                                  _p, _p]),
     "asrx_row_tiles_max": (_i64, [_i64]),
@@ -121,6 +123,10 @@ SIGNATURES = {
     "asrx_msheath_ctrl_bwd4": (_i32, [_p, _i64, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i32]
                                + [_p] * 8),
     "asrx_axpy_row2_bwd_acc": (_i32, [_p, _p, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "asrx_jump_select4_bwd_part2": (_i32, [_p] * 11 + [_i64, _i64, _i64, _p]),
+    "asrx_jump_select4_bwd_acc2": (_i32, [_p] * 13 + [_i64, _i64, _i64, _p]),
+    "asrx_axpy_row2_bwd_acc2": (_i32, [_p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "asrx_wgrad_split": (_i32, [_p, _i64, _p, _i32, _i64, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p]),
     "asrx_msheath_dx_final": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_axpy_row2": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _p]),
     "asrx_axpy_row2_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),

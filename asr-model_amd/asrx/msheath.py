@@ -46,6 +46,14 @@ DETERMINISTIC = True
 # A layer without adapter (its update is px itself) forms x_new and the per-chunk column sums in its row pass
 # (asrx_msheath_row_fwd3) instead of a separate asrx_axpy_row2_colsum launch.  False: the two-launch form.
 ROW_COLSUM = __import__("os").environ.get("ASRX_ROW_COLSUM", "1") != "0"
+# The layer backward with fewer layer-sized passes: the jump backward stores no dxn = alpha g (the x_new backward takes
+# g and alpha, asrx_axpy_row2_bwd_acc2); on a layer without adapter the row backward forms g' = alpha g + g_mem / L
+# itself and does the x_new backward on a recomputed px (asrx_msheath_row_bwd2 mode 2: no asrx_axpy_row2_bwd_acc launch,
+# and the forward stores no px there); v_gate's two weight gradients are one launch (gemm.wgrad_cols2).  False: the
+# six-step form.
+BWD_FUSED = __import__("os").environ.get("ASRX_MSHEATH_BWD_FUSED", "1") != "0"
+# Measurement only (DESIGN.md §7 measures BWD_FUSED's weight-gradient part apart with it; nothing else sets it).
+WGRAD_MERGED = __import__("os").environ.get("ASRX_MSHEATH_WGRAD_MERGED", "1") != "0"
 
 
 def _rec_bytes():
@@ -113,6 +121,7 @@ def forward(mod, x0, gpol, save, tag=None):
     a_r, a_b, a_d, a_c = wsr.data_ptr(), wsb.data_ptr(), wsd.data_ptr(), wsc.data_ptr()
     if save:
         sv["ws"] = (wsr, wsb, wsd, wsc)
+        sv["bwd_fused"] = BWD_FUSED  # the backward follows what this forward stored
     inv_sqrt_d = 1.0 / math.sqrt(D)
     layers = []
     for i, lay in enumerate(mod.layers):
@@ -139,7 +148,9 @@ def forward(mod, x0, gpol, save, tag=None):
         ad = lay["adapter"]
         # px feeds only the adapter GEMM on even layers (bf16-stored); on odd layers it is the update itself
         pxb = int(ad is not None and wide and prec.bf16_storage())
-        px = _E(B, L, D, device=dev, dtype=torch.bfloat16 if pxb else torch.float32)
+        # (not stored at all where the fused backward recomputes it: x_new is stored and px has no other reader)
+        no_px = save and BWD_FUSED and ad is None and ROW_COLSUM
+        px = None if no_px else _E(B, L, D, device=dev, dtype=torch.bfloat16 if pxb else torch.float32)
         mean, rstd, nx, gv, ion, kv, m2 = (a_r + 4 * rows * (7 * i + j) for j in range(7))
         # x_new = x + g * ion * out; mem = mean_l x_new   (461-463).  Without a backward x_new is not
         # materialised: the column sums are taken and the jump step below recomputes it
@@ -268,6 +279,7 @@ class MSheathFn(torch.autograd.Function):
         g_mwo = None
         mg_w, mg_b = mod.mem_gate[0].weight, mod.mem_gate[0].bias
         inv_sqrt_d = 1.0 / math.sqrt(D)
+        fused = sv["bwd_fused"]
         for i in range(nl - 1, -1, -1):
             s = sv["layers"][i]
             lay = mod.layers[i]
@@ -276,13 +288,13 @@ class MSheathFn(torch.autograd.Function):
             N = M + Dh
             xi = s["x"]
             dxi = _E(B, L, D, device=dev)
-            dxn = _E(B, L, D, device=dev)
+            dxn = None if fused else _E(B, L, D, device=dev)  # fused: alpha g is formed by its consumers
             g_mem_w, g_mem = _E(B, D, device=dev), _E(B, D, device=dev)
             if DETERMINISTIC:  # per-chunk partials summed in order by the control backward
                 part = _E(int(lib.load().asrx_jump_bwd_part_floats(B, L, D)), device=dev)
-                lib.call("asrx_jump_select4_bwd_part", _P(dx), _P(s["x_new"]), _P(x0), _P(s["active"]),
-                         _P(s["alpha"]), _P(s["beta"]), _P(has_orig), _P(dxn), _P(dorig), _P(dxi), _P(part), B, L, D,
-                         st)
+                lib.call("asrx_jump_select4_bwd_part2" if fused else "asrx_jump_select4_bwd_part",
+                         _P(dx), _P(s["x_new"]), _P(x0), _P(s["active"]), _P(s["alpha"]), _P(s["beta"]), _P(has_orig),
+                         _P(dxn), _P(dorig), _P(dxi), _P(part), B, L, D, st)
                 lib.call("asrx_msheath_ctrl_bwd4", _P(part), L, _P(g_mwo), _P(s["mem_v"]), _P(s["mem_w"]),
                          s["ld_mw"], _P(s["mem"]), _P(mod.jump_s), _P(s["rec"]), i, nl, B, D, _P(g_policy),
                          int(i != nl - 1), _P(g_mem_w), _P(g_mem), _P(gb(mod.jump_s)), _P(has_orig), _P(mg_w),
@@ -290,19 +302,27 @@ class MSheathFn(torch.autograd.Function):
             else:
                 dctl = _E(B * (2 + D), device=dev)  # [dalpha | dbeta | dgam]: zeroed by one memset
                 dalpha, dbeta, dgam = dctl[:B], dctl[B:2 * B], dctl[2 * B:]
-                lib.call("asrx_jump_select4_bwd_acc", _P(dx), _P(s["x_new"]), _P(x0), _P(s["active"]),
-                         _P(s["alpha"]), _P(s["beta"]), _P(has_orig), _P(dxn), _P(dorig), _P(dxi), _P(dalpha),
-                         _P(dbeta), _P(dgam), B, L, D, st)
+                lib.call("asrx_jump_select4_bwd_acc2" if fused else "asrx_jump_select4_bwd_acc",
+                         _P(dx), _P(s["x_new"]), _P(x0), _P(s["active"]), _P(s["alpha"]), _P(s["beta"]), _P(has_orig),
+                         _P(dxn), _P(dorig), _P(dxi), _P(dalpha), _P(dbeta), _P(dgam), B, L, D, st)
                 lib.call("asrx_msheath_ctrl_bwd3", _P(dalpha), _P(dbeta), _P(dgam), _P(g_mwo), _P(s["mem_v"]),
                          _P(s["mem_w"]), s["ld_mw"], _P(s["mem"]), _P(mod.jump_s), _P(s["rec"]), i, nl, B, D,
                          _P(g_policy), int(i != nl - 1), _P(g_mem_w), _P(g_mem), _P(gb(mod.jump_s)), _P(has_orig),
                          _P(mg_w), _P(gb(mg_w)), _P(gb(mg_b)), st)
-            dout = _E(B, L, D, device=dev)
-            dgv, dion = _E(rows, device=dev), _E(rows, device=dev)
-            lib.call("asrx_axpy_row2_bwd_acc", _P(dxn), _P(g_mem), 1.0 / L, _P(s["active"]), _P(s["g"]), _P(s["ion"]),
-                     _P(s["out"]), _P(dout), _P(dgv), _P(dion), _P(dxi), B, L, D, st)
-            del dxn
             ad = lay["adapter"]
+            mode = 2 if fused and ad is None else 0  # asrx_msheath_row_bwd2's mode
+            dout = dgv = dion = None
+            if not fused:
+                dout = _E(B, L, D, device=dev)
+                dgv, dion = _E(rows, device=dev), _E(rows, device=dev)
+                lib.call("asrx_axpy_row2_bwd_acc", _P(dxn), _P(g_mem), 1.0 / L, _P(s["active"]), _P(s["g"]),
+                         _P(s["ion"]), _P(s["out"]), _P(dout), _P(dgv), _P(dion), _P(dxi), B, L, D, st)
+            elif ad is not None:  # the same from (g, alpha) instead of dxn
+                dout = _E(B, L, D, device=dev)
+                dgv, dion = _E(rows, device=dev), _E(rows, device=dev)
+                lib.call("asrx_axpy_row2_bwd_acc2", _P(dx), _P(s["alpha"]), _P(g_mem), 1.0 / L, _P(s["active"]),
+                         _P(s["g"]), _P(s["ion"]), _P(s["out"]), _P(dout), _P(dgv), _P(dion), _P(dxi), B, L, D, st)
+            del dxn
             if ad is not None:
                 dpx = G.linear_dgrad(dout, ad.weight, mtiles=s["mt"])  # rows off the layer: not read below
                 G.linear_wgrad(dout, s["px"], out=gb(ad.weight), accumulate=True, db=gb(ad.bias))
@@ -311,22 +331,33 @@ class MSheathFn(torch.autograd.Function):
             # LayerNorm + gate + |x| + v_gate backward in one row pass; dSH = [dS | dh]
             ln, gt = lay["ln"], lay["gate"][0]
             dSH = _E(rows, N, device=dev)
-            lib.call("asrx_msheath_row_bwd", _P(dpx), _P(xi), _P(ln.weight), _P(ln.bias), _P(s["mean"]),
-                     _P(s["rstd"]), _P(dgv), _P(s["g"]), _P(gt.weight), _P(dion), _P(s["SH"]), N, _P(s["nx"]),
-                     _P(vg.mval), _P(vg.mlp[2].weight), _P(vg.concat.weight), _P(s["kv"]), _P(s["m2"]), _P(dxi),
-                     _P(gb(ln.weight)), _P(gb(ln.bias)), _P(gb(gt.weight)), _P(gb(gt.bias)), _P(dSH),
-                     _P(gb(vg.mval)), _P(gb(vg.mlp[2].weight)), _P(gb(vg.mlp[2].bias)), _P(gb(vg.concat.weight)),
-                     _P(gb(vg.concat.bias)), _P(gb(vg.mlp[0].bias)), rows, D, M, Dh, inv_sqrt_d, _P(s["next_i"]), i,
-                     L, st)
+            row_args = (_P(dpx), _P(xi), _P(ln.weight), _P(ln.bias), _P(s["mean"]), _P(s["rstd"]), _P(dgv), _P(s["g"]),
+                        _P(gt.weight), _P(dion), _P(s["SH"]), N, _P(s["nx"]), _P(vg.mval), _P(vg.mlp[2].weight),
+                        _P(vg.concat.weight), _P(s["kv"]), _P(s["m2"]), _P(dxi), _P(gb(ln.weight)), _P(gb(ln.bias)),
+                        _P(gb(gt.weight)), _P(gb(gt.bias)), _P(dSH), _P(gb(vg.mval)), _P(gb(vg.mlp[2].weight)),
+                        _P(gb(vg.mlp[2].bias)), _P(gb(vg.concat.weight)), _P(gb(vg.concat.bias)),
+                        _P(gb(vg.mlp[0].bias)), rows, D, M, Dh, inv_sqrt_d, _P(s["next_i"]), i, L, st)
+            if mode:
+                # no adapter (dpx, dgv, dion are None): dxi's base g' formed from (dx, alpha, g_mem / L) in the row
+                # pass, which is dxi's first writer for samples at the layer, and the x_new backward done there on px
+                # recomputed from x, mean and rstd
+                lib.call("asrx_msheath_row_bwd2", mode, _P(dx), _P(s["alpha"]), _P(g_mem),
+                         1.0 / L, _P(s["ion"]), *row_args)
+            else:
+                lib.call("asrx_msheath_row_bwd", *row_args)
             del dout, dpx
             # x's gradient through both projections: one GEMM against [normalize(mkey); mlp[0].weight]
             G.linear_dgrad(dSH, s["Wc"], out=dxi, beta=1.0, mtiles=s["mt"])
             x2 = xi.view(rows, D)
             dmk = _E(M, D, device=dev)
             lib.call("asrx_zero", _P(dmk), dmk.numel() * 4, st)
-            G.wgrad_cols(dSH, 0, M, x2, dmk)
-            lib.call("asrx_row_normalize_bwd", _P(dmk), _P(s["Wc"]), _P(s["mkn"]), _P(gb(vg.mkey)), M, D, 1, st)
-            G.wgrad_cols(dSH, M, Dh, x2, gb(vg.mlp[0].weight))
+            if fused and WGRAD_MERGED:  # both column blocks of dSH^T x in one pass over dSH and x
+                G.wgrad_cols2(dSH, M, dmk, gb(vg.mlp[0].weight), x2)
+                lib.call("asrx_row_normalize_bwd", _P(dmk), _P(s["Wc"]), _P(s["mkn"]), _P(gb(vg.mkey)), M, D, 1, st)
+            else:
+                G.wgrad_cols(dSH, 0, M, x2, dmk)
+                lib.call("asrx_row_normalize_bwd", _P(dmk), _P(s["Wc"]), _P(s["mkn"]), _P(gb(vg.mkey)), M, D, 1, st)
+                G.wgrad_cols(dSH, M, Dh, x2, gb(vg.mlp[0].weight))
             del dSH, dmk
             g_mwo = g_mem_w
             dx = dxi

@@ -36,6 +36,11 @@ struct Params {
   // optional bias gradient (asrx_wgrad_bias): db[m] += sum over rows of dY[:, m], summed from the dY
   // stages this kernel loads anyway (column tile 0 only), instead of a separate column-sum pass
   float* db;
+  // split destination (asrx_wgrad_split): output rows m >= msplit are added into C2 + (m - msplit) ldc2 instead --
+  // one pass over dY and X for two weight gradients that share X (v_gate's mkey and mlp[0] blocks)
+  float* C2 = nullptr;
+  int64_t ldc2 = 0;
+  int msplit = 0;
 };
 
 // byte offset of 16-B chunk ch (8 features) of k-row `row` in a [32][128] bf16 image
@@ -191,7 +196,7 @@ __device__ __forceinline__ void colacc(const Stage<ABF, BBF>& st, float (&cs)[8]
   }
 }
 
-template <bool ABF, bool BBF>
+template <bool ABF, bool BBF, bool SPLIT = false>
 __global__ __launch_bounds__(NT, 2) void wgrad_wr_kernel(Params p) {
   __shared__ __attribute__((aligned(16))) char Ai[2][TK * TM * 2];
   __shared__ __attribute__((aligned(16))) char Bi[2][TK * TN * 2];
@@ -256,7 +261,12 @@ __global__ __launch_bounds__(NT, 2) void wgrad_wr_kernel(Params p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = m0 + wm * 64 + mt * 16 + lm + r;
-        if (m < p.M && nk > 0) atomicAdd(p.C + (int64_t)m * p.ldc + n, acc[mt][nt][r]);
+        if constexpr (SPLIT) {
+          float* row = m < p.msplit ? p.C + (int64_t)m * p.ldc : p.C2 + (int64_t)(m - p.msplit) * p.ldc2;
+          if (m < p.M && nk > 0) atomicAdd(row + n, acc[mt][nt][r]);
+        } else {
+          if (m < p.M && nk > 0) atomicAdd(p.C + (int64_t)m * p.ldc + n, acc[mt][nt][r]);
+        }
       }
     }
   if (dbon && nk > 0) {
@@ -562,6 +572,32 @@ extern "C" int asrx_wgrad_bf16_ex(const float* A, int64_t lda, const void* B, in
 extern "C" int asrx_wgrad_bf16_ab(const void* A, int64_t lda, const void* B, int b_bf16, int64_t ldb, float* C,
                                   int64_t ldc, int64_t M, int64_t N, int64_t R, int64_t splitk, hipStream_t stream) {
   return wgrad_launch(A, 1, lda, B, b_bf16, ldb, C, ldc, M, N, R, splitk, stream);
+}
+
+// asrx_wgrad_bf16_ex with two destinations: rows m < msplit of dY^T X are added into C (msplit x N, ldc), rows
+// msplit <= m < M into C2 ((M - msplit) x N, ldc2).  Always the 128 x 128-item kernel.
+extern "C" int asrx_wgrad_split(const float* A, int64_t lda, const void* B, int b_bf16, int64_t ldb, float* C,
+                                int64_t ldc, float* C2, int64_t ldc2, int64_t msplit, int64_t M, int64_t N, int64_t R,
+                                int64_t splitk, hipStream_t stream) {
+  ASRX_REQUIRE(M > 0 && N > 0 && R >= 0, "asrx_wgrad_split: empty problem");
+  ASRX_REQUIRE(msplit > 0 && msplit < M && C && C2, "asrx_wgrad_split: 0 < msplit < M and both destinations required");
+  ASRX_REQUIRE(M % 4 == 0 && N % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0, "asrx_wgrad_split: M, N, lda, ldb %% 4 required");
+  ASRX_REQUIRE(!b_bf16 || (N % 8 == 0 && ldb % 8 == 0), "asrx_wgrad_split: a bf16 X needs N, ldb %% 8");
+  ASRX_REQUIRE((((uintptr_t)A | (uintptr_t)B) & 15) == 0, "asrx_wgrad_split: operands must be 16-byte aligned");
+  if (R == 0) return 0;
+  if (splitk < 1) splitk = 1;
+  int64_t kchunk = (R + splitk - 1) / splitk;
+  kchunk = (kchunk + wg::TK - 1) / wg::TK * wg::TK;
+  splitk = (R + kchunk - 1) / kchunk;
+  wg::Params p{A, (const float*)B, C, lda, ldb, ldc, (int)M, (int)N, R, kchunk, (int)splitk, nullptr, C2, ldc2,
+               (int)msplit};
+  const int64_t items = ((M + wg::TM - 1) / wg::TM) * ((N + wg::TN - 1) / wg::TN) * splitk;
+  ASRX_REQUIRE(items < (1LL << 31), "asrx_wgrad_split: too many work items");
+  if (b_bf16)
+    wg::wgrad_wr_kernel<false, true, true><<<(unsigned)items, wg::NT, 0, stream>>>(p);
+  else
+    wg::wgrad_wr_kernel<false, false, true><<<(unsigned)items, wg::NT, 0, stream>>>(p);
+  ASRX_LAUNCHED("asrx_wgrad_split");
 }
 
 // dW += dY^T X and db += column sums of dY in one pass (the bias gradient of y = x W^T + b summed from

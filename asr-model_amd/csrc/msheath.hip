@@ -489,7 +489,8 @@ __global__ __launch_bounds__(256) void jump_select4_bwd_kernel(
 // x_i lands in ONE buffer -- written by the first producer, accumulated by the rest -- instead of
 // separate tensors that autograd sums with extra add kernels.
 //
-// jump_select backward, accumulate form.  Active samples: dxn = alpha g; orig's gradient
+// jump_select backward, accumulate form.  Active samples: dxn = alpha g (not written when dxn is null:
+// the consumers then form alpha g themselves, asrx_axpy_row2_bwd_acc2 / asrx_msheath_row_bwd2 mode 2); orig's gradient
 // dorig (+)= beta g only when beta != 0 (a jump), the first jumping layer of a sample writing
 // (has_orig[b] == 0, set afterwards by msheath_ctrl_bwd); x_i's gradient is left to
 // axpy_row2_bwd_acc.  Inactive samples: dx = g (the pass-through), nothing else.
@@ -523,7 +524,7 @@ __global__ __launch_bounds__(256) void jump_select4_bwd_acc_kernel(
         sa += gv.x * u.x + gv.y * u.y + gv.z * u.z + gv.w * u.w;
         sb += gv.x * v.x + gv.y * v.y + gv.z * v.z + gv.w * v.w;
         sgv.x += gv.x; sgv.y += gv.y; sgv.z += gv.z; sgv.w += gv.w;
-        dxn[i] = make_float4(al * gv.x, al * gv.y, al * gv.z, al * gv.w);
+        if (dxn) dxn[i] = make_float4(al * gv.x, al * gv.y, al * gv.z, al * gv.w);
         if (jo) {
           float4 o = make_float4(be * gv.x, be * gv.y, be * gv.z, be * gv.w);
           if (acc_o) {
@@ -577,13 +578,16 @@ __global__ __launch_bounds__(256) void jump_select4_bwd_acc_kernel(
 // samples: g' = dxn + gm[b] / L (the seg-mean broadcast folded in), dy = s1 s2 g', ds1 = s2 g'.y,
 // ds2 = s1 g'.y, and dx = g' -- the first contribution to x_i of an active sample.  Inactive
 // samples: dy = 0, ds = 0, dx untouched (jump_select4_bwd_acc wrote the pass-through).
+// alpha non-null: dxn is the jump's incoming gradient g and dxn = alpha[b] g is formed here (the same product
+// jump_select4_bwd_acc would have stored).
 __global__ __launch_bounds__(256) void axpy_row2_bwd_acc_kernel(const float4* __restrict__ dxn,
                                                                 const float* __restrict__ gm, float invL,
                                                                 const float* __restrict__ act,
                                                                 const float* __restrict__ s1, const float* __restrict__ s2,
                                                                 const float4* __restrict__ y, float4* __restrict__ dy,
                                                                 float* __restrict__ ds1, float* __restrict__ ds2,
-                                                                float4* __restrict__ dx, int64_t rows, int64_t L, int d4) {
+                                                                float4* __restrict__ dx, int64_t rows, int64_t L, int d4,
+                                                                const float* __restrict__ alpha = nullptr) {
   const int lane = threadIdx.x & 63;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
@@ -599,9 +603,11 @@ __global__ __launch_bounds__(256) void axpy_row2_bwd_acc_kernel(const float4* __
     const float a = s1[r], c = s2 ? s2[r] : 1.f;
     const float sc = a * c;
     const float4* gm4 = reinterpret_cast<const float4*>(gm + b * 4 * d4);
+    const float al = alpha ? alpha[b] : 1.f;
     float t = 0.f;
     for (int j = lane; j < d4; j += 64) {
       float4 gv = dxn[r * d4 + j];
+      if (alpha) gv = make_float4(al * gv.x, al * gv.y, al * gv.z, al * gv.w);
       if (gm) {
         const float4 m = gm4[j];
         gv.x += m.x * invL; gv.y += m.y * invL; gv.z += m.z * invL; gv.w += m.w * invL;
@@ -703,6 +709,23 @@ int asrx_jump_select4_bwd_part(const float* g, const float* xn, const float* ori
   ASRX_LAUNCHED("asrx_jump_select4_bwd_part");
 }
 
+// asrx_jump_select4_bwd_part that may leave dxn = alpha g unwritten (dxn null): one activation-sized store less
+// when the x_new backward and the row backward take g and alpha instead (asrx/msheath.py BWD_FUSED).
+int asrx_jump_select4_bwd_part2(const float* g, const float* xn, const float* orig, const float* act,
+                                const float* alpha, const float* beta, const int* has_orig, float* dxn, float* dorig,
+                                float* dx, float* part, int64_t B, int64_t L, int64_t d, hipStream_t stream) {
+  return asrx_jump_select4_bwd_part(g, xn, orig, act, alpha, beta, has_orig, dxn, dorig, dx, part, B, L, d, stream);
+}
+
+// The atomic form with the same optional dxn.
+int asrx_jump_select4_bwd_acc2(const float* g, const float* xn, const float* orig, const float* act,
+                               const float* alpha, const float* beta, const int* has_orig, float* dxn, float* dorig,
+                               float* dx, float* dalpha, float* dbeta, float* dgam, int64_t B, int64_t L, int64_t d,
+                               hipStream_t stream) {
+  return asrx_jump_select4_bwd_acc(g, xn, orig, act, alpha, beta, has_orig, dxn, dorig, dx, dalpha, dbeta, dgam, B, L,
+                                   d, stream);
+}
+
 int asrx_axpy_row2_bwd_acc(const float* dxn, const float* gm, float invL, const float* act, const float* s1,
                            const float* s2, const float* y, float* dy, float* ds1, float* ds2, float* dx, int64_t B,
                            int64_t L, int64_t d, hipStream_t stream) {
@@ -713,6 +736,22 @@ int asrx_axpy_row2_bwd_acc(const float* dxn, const float* gm, float invL, const 
       (const float4*)dxn, gm, invL, act, s1, s2, (const float4*)y, (float4*)dy, ds1, ds2, (float4*)dx, rows, L,
       (int)(d / 4));
   ASRX_LAUNCHED("asrx_axpy_row2_bwd_acc");
+}
+
+// asrx_axpy_row2_bwd_acc from the jump's incoming gradient g and alpha (B) instead of the stored dxn = alpha g:
+// g' = alpha[b] g + gm[b] / L with the same roundings; writes dy, ds1, ds2 and dx = g' (an adapter layer, ahead of
+// asrx_msheath_row_bwd).
+int asrx_axpy_row2_bwd_acc2(const float* g, const float* alpha, const float* gm, float invL, const float* act,
+                            const float* s1, const float* s2, const float* y, float* dy, float* ds1, float* ds2,
+                            float* dx, int64_t B, int64_t L, int64_t d, hipStream_t stream) {
+  ASRX_REQUIRE(d % 4 == 0, "asrx_axpy_row2_bwd_acc2: d % 4 != 0");
+  ASRX_REQUIRE(alpha && dx, "asrx_axpy_row2_bwd_acc2: alpha and dx required");
+  const int64_t rows = B * L;
+  if (rows == 0) return 0;
+  axpy_row2_bwd_acc_kernel<<<(unsigned)std::min<int64_t>((rows + 3) / 4, 8192), 256, 0, stream>>>(
+      (const float4*)g, gm, invL, act, s1, s2, (const float4*)y, (float4*)dy, ds1, ds2, (float4*)dx, rows, L,
+      (int)(d / 4), alpha);
+  ASRX_LAUNCHED("asrx_axpy_row2_bwd_acc2");
 }
 
 int asrx_msheath_dx_final(float* dx, const float* dorig, const int* has_orig, const float* u, int64_t B, int64_t L,

@@ -644,7 +644,7 @@ struct MSRowFwd {
   const float* next_i;  // rows of samples b with next_i[b] != layer are not at this layer (null: all are)
   int layer;
   int64_t L;
-  unsigned short* pxb;  // non-null: px stored bf16 here instead (it only feeds the adapter GEMM)
+  unsigned short* pxb;  // non-null: px stored bf16 here instead (it only feeds the adapter GEMM); both null: no store
   // non-null (a layer without adapter, whose update is px itself): x_new = x + g ion px (model.py:461) is formed
   // per row and its per-sample column sums over 64-row chunks go to part[b][chunk][:] -- the work of
   // axpy_row2_colsum (msheath.hip) in this pass; each wave then owns whole chunks (rows in order), and xnew (when
@@ -709,7 +709,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
 #pragma unroll
       for (int e = 0; e < E; ++e) z[e] = 0.f;
       if (p.pxb) st_lane<E>(p.pxb + r * D, lane, z);
-      else st_lane<E>(p.px + r * D, lane, z);
+      else if (p.px) st_lane<E>(p.px + r * D, lane, z);
       if (lane == 0) {
         p.mean[r] = 0.f;
         p.rstd[r] = 0.f;
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
       gd += yv[e] * gwv[e];
     }
     if (p.pxb) st_lane<E>(p.pxb + r * D, lane, yv);
-    else st_lane<E>(p.px + r * D, lane, yv);
+    else if (p.px) st_lane<E>(p.px + r * D, lane, yv);  // null (row_fwd3 with xnew): px has no reader
     const float ez = lane < p.M ? expf(z - zm) : 0.f;
     float se = ez;
     wave_sum2_dpp(gd, se);
@@ -876,6 +876,11 @@ struct MSRowBwd {
   const float* next_i;  // as MSRowFwd: rows of samples not at this layer get dSH = 0 and nothing else
   int layer;
   int64_t L;
+  // mode 2 (asrx_msheath_row_bwd2; a layer without adapter, whose update is px itself): dx's base
+  // g' = alpha[b] gj + gm[b, :] invL is formed here from the jump's incoming gradient gj, not loaded from dx (as
+  // axpy_row2_bwd_acc wrote it), and dpx, dg and dion are formed from g', the recomputed px, g and ion
+  const float *gj = nullptr, *alpha = nullptr, *gm = nullptr, *ion = nullptr;
+  float invL = 0.f;
 };
 
 // Per row, the backward of msheath_row_fwd: v_gate (dSH row with stride ldsh: dS already divided by
@@ -883,7 +888,11 @@ struct MSRowBwd {
 // term in its output gradient, and |x|'s gradient, all accumulated into dx; parameter gradients
 // (ln w/b, gate w/b, mval, mlp[2] w/b, concat w/b, mlp[0].bias) as workgroup partials + atomics.
 // Dynamic LDS: RW * (3 D + M + 2 Dh + 5) floats.
-template <int E>
+// MODE 0: dx holds its base (axpy_row2_bwd_acc's g') and is accumulated into.  MODE 2: the base is formed from gj,
+// alpha, gm, invL with axpy_row2_bwd_acc's roundings, dx is only written, and the x_new backward of a layer whose
+// update is px is done here: t = g' . px, dion = g t, dg = ion t, dpx = (g ion) g'.  (There is no mode 1: forming
+// the base here while keeping the x_new backward kernel measured no gain)
+template <int E, int MODE = 0>
 __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
   constexpr int D = 64 * E;
   extern __shared__ float part[];
@@ -907,8 +916,9 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
   // next_i (a global load inside the loop would drain the prefetch queue at its wait).
   constexpr int HQ = (E + 1) / 2;  // h values per lane (Dh <= 64 HQ)
   struct Pre {
-    float x[E], gp[E], dx[E], h[HQ];
-    float s, gi, nx, g, dg, mu, rs, kv, m2;
+    float x[E], gp[E], dx[E], gm[E], h[HQ];  // MODE 2: dx holds gj's row; a field a mode never loads is dropped
+                                             // by the compiler (mode 0's register count is the parent's)
+    float s, gi, nx, g, dg, mu, rs, kv, m2, al, ion;
   };
   const int ni_off = RW * (3 * D + PN);  // next_i copy (one float per sample) after the partials
   if (p.next_i) {
@@ -932,12 +942,23 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
 #pragma unroll
     for (int i = 0; i < HQ; ++i) q.h[i] = S[M + min(lane + 64 * i, Dh - 1)];
     ld_lane<E>(p.x + rc * D, lane, q.x);
-    ld_lane<E>(p.dpx + rc * D, lane, q.gp);
-    ld_lane<E>(p.dx + rc * D, lane, q.dx);
-    q.gi = p.dion[rc];
+    if constexpr (MODE != 2) ld_lane<E>(p.dpx + rc * D, lane, q.gp);
+    if constexpr (MODE == 0) {
+      ld_lane<E>(p.dx + rc * D, lane, q.dx);
+    } else {
+      const int64_t bc = (int64_t)((unsigned)rc / (unsigned)p.L);
+      ld_lane<E>(p.gj + rc * D, lane, q.dx);
+      ld_lane<E>(p.gm + bc * D, lane, q.gm);
+      q.al = p.alpha[bc];
+    }
+    if constexpr (MODE == 2) {
+      q.ion = p.ion[rc];
+    } else {
+      q.gi = p.dion[rc];
+      q.dg = p.dg[rc];
+    }
     q.nx = p.nx[rc];
     q.g = p.g[rc];
-    q.dg = p.dg[rc];
     q.mu = p.mean[rc];
     q.rs = p.rstd[rc];
     q.kv = p.kv[rc];
@@ -956,8 +977,39 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
       for (int j = lane; j < M + Dh; j += 64) dz[j] = 0.f;
       return;
     }
+    // dx's base: MODE 0 what dx holds; else g' = alpha gj + gm invL, each product rounded on its own as
+    // jump_select4_bwd_acc (dxn = alpha g) and axpy_row2_bwd_acc (dxn + gm invL) do (this unit builds without
+    // contractions)
+    float base[E], gpx[E];
+    float gi_r = 0.f, dg_r = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      if constexpr (MODE == 0) {
+        base[e] = c.dx[e];
+      } else {
+        const float dxn = c.al * c.dx[e];
+        const float gmL = c.gm[e] * p.invL;
+        base[e] = dxn + gmL;
+      }
+      if constexpr (MODE != 2) gpx[e] = c.gp[e];
+    }
+    if constexpr (MODE == 2) {
+      // x_new = x + (g ion) px backward with px recomputed by the forward's own fma (bit-equal to the stored one)
+      float t = 0.f;
+#pragma unroll
+      for (int e = 0; e < E; ++e) t += base[e] * __builtin_fmaf((c.x[e] - c.mu) * c.rs, wv[e], bv[e]);
+      t = wave_sum_dpp(t);
+      const float sc = c.g * c.ion;
+      gi_r = c.g * t;
+      dg_r = c.ion * t;
+#pragma unroll
+      for (int e = 0; e < E; ++e) gpx[e] = sc * base[e];
+    } else {
+      gi_r = c.gi;
+      dg_r = c.dg;
+    }
     // ---- v_gate backward (vgate_bwd_kernel)
-    const float gi = c.gi;
+    const float gi = gi_r;
     const float nxr = c.nx;
     const float inx = 1.0f / fmaxf(nxr, 1e-12f);
     float* dS = p.dSH + r * p.ldsh;
@@ -990,7 +1042,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
     }
     // ---- gate + LayerNorm + |x| backward
     const float gg = c.g;
-    const float dzg = c.dg * gg * (1.f - gg);
+    const float dzg = dg_r * gg * (1.f - gg);
     if (lane == 0) {
       pw[M + 2 * Dh + 0] += dm2;
       pw[M + 2 * Dh + 1] += gi * c.kv;
@@ -1002,7 +1054,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       xv[e] = c.x[e];
-      gv[e] = c.gp[e];
+      gv[e] = gpx[e];
     }
     const float mu = c.mu, rs = c.rs;
     const float cn = nxr > 0.f ? dnx / nxr : 0.f;
@@ -1023,7 +1075,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
     s2 *= (1.0f / D);
     float dv[E];
 #pragma unroll
-    for (int e = 0; e < E; ++e) dv[e] = c.dx[e] + rs * (gv[e] * wv[e] - s1 - xh[e] * s2) + cn * xv[e];
+    for (int e = 0; e < E; ++e) dv[e] = base[e] + rs * (gv[e] * wv[e] - s1 - xh[e] * s2) + cn * xv[e];
     st_lane<E>(p.dx + r * D, lane, dv);
   };
   for (int64_t r = r0; r < p.rows; r += 2 * st) {
@@ -2754,6 +2806,8 @@ int asrx_msheath_row_fwd3(const float* x, const float* lnw, const float* lnb, co
   ASRX_REQUIRE(ms_aligned({x, lnw, lnb, gw, (const float*)px, (const float*)xnew, (const float*)part}),
                "asrx_msheath_row_fwd3: 8-byte aligned rows required");
   ASRX_REQUIRE(part && L > 0 && rows % L == 0, "asrx_msheath_row_fwd3: part and rows = B L required");
+  // px may be null when xnew is given: the backward of such a layer recomputes px (asrx_msheath_row_bwd2 mode 2)
+  ASRX_REQUIRE(px || xnew, "asrx_msheath_row_fwd3: px or xnew required");
   if (rows == 0) return 0;
   MSRowFwd p{x, lnw, lnb, gw, gb, SH, mval, w2, b2, cw, cb, tx, px, mean, rstd, nx, g, ion, kv, m2, rows, ldsh,
              (int)M, (int)Dh, eps, inv_sqrt_d, next_i, (int)layer, L, nullptr, part, xnew, (int)((L + 63) / 64),
@@ -2799,6 +2853,51 @@ int asrx_msheath_row_bwd(const float* dpx, const float* x, const float* lnw, con
   MS_DISPATCH(msheath_row_bwd_kernel, row_grid(rows, 1024), shm, p);
   ASRX_LAUNCHED("asrx_msheath_row_bwd");
 }
+
+#define MS_DISPATCH_MODE(MODE, GRID, SHM, P)                                                        \
+  switch (d) {                                                                                      \
+    case 128: msheath_row_bwd_kernel<2, MODE><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 256: msheath_row_bwd_kernel<4, MODE><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 384: msheath_row_bwd_kernel<6, MODE><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 512: msheath_row_bwd_kernel<8, MODE><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 768: msheath_row_bwd_kernel<12, MODE><<<GRID, 64 * RW, SHM, stream>>>(P); break;           \
+    case 1024: msheath_row_bwd_kernel<16, MODE><<<GRID, 64 * RW, SHM, stream>>>(P); break;          \
+    default: ASRX_REQUIRE(false, "asrx_msheath_row_bwd2: d=%ld unsupported", (long)d);              \
+  }
+
+// asrx_msheath_row_bwd that, in mode 2 (no adapter, update = px), forms dx's base g' = alpha[b] gj + gm[b, :] invL
+// itself (gj: the gradient arriving at the layer's jump select, alpha (B), gm (B x d)) instead of reading it from
+// dx, which it only writes (rows of samples at the layer; others untouched as before), and does the x_new backward
+// per row on a recomputed px, which needs ion: dpx, dg, dion are not read.  mode 0: asrx_msheath_row_bwd.
+int asrx_msheath_row_bwd2(int mode, const float* gj, const float* alpha, const float* gm, float invL,
+                          const float* ion, const float* dpx, const float* x, const float* lnw, const float* lnb,
+                          const float* mean, const float* rstd, const float* dg, const float* g, const float* gw,
+                          const float* dion, const float* SH, int64_t ldsh, const float* nx, const float* mval,
+                          const float* w2, const float* cw, const float* kv, const float* m2, float* dx, float* dlnw,
+                          float* dlnb, float* dgw, float* dgb, float* dSH, float* dmval, float* dw2, float* db2,
+                          float* dcw, float* dcb, float* db1, int64_t rows, int64_t d, int64_t M, int64_t Dh,
+                          float inv_sqrt_d, const float* next_i, int64_t layer, int64_t L, hipStream_t stream) {
+  if (mode == 0)
+    return asrx_msheath_row_bwd(dpx, x, lnw, lnb, mean, rstd, dg, g, gw, dion, SH, ldsh, nx, mval, w2, cw, kv, m2, dx,
+                                dlnw, dlnb, dgw, dgb, dSH, dmval, dw2, db2, dcw, dcb, db1, rows, d, M, Dh, inv_sqrt_d,
+                                next_i, layer, L, stream);
+  ASRX_REQUIRE(mode == 2, "asrx_msheath_row_bwd2: mode 0 or 2");
+  ASRX_REQUIRE(M <= 64 && ldsh >= M + Dh, "asrx_msheath_row_bwd2: M <= 64 and ldsh >= M + Dh required");
+  ASRX_REQUIRE(Dh <= 64 * ((d / 64 + 1) / 2), "asrx_msheath_row_bwd2: v_gate hidden size Dh <= d / 2 required");
+  ASRX_REQUIRE(gj && alpha && gm && L > 0 && rows % L == 0, "asrx_msheath_row_bwd2: gj, alpha, gm and rows = B L required");
+  ASRX_REQUIRE(ion, "asrx_msheath_row_bwd2: mode 2 reads ion");
+  ASRX_REQUIRE(ms_aligned({gj, gm, dpx, x, lnw, lnb, gw, dx}), "asrx_msheath_row_bwd2: 8-byte aligned rows required");
+  if (rows == 0) return 0;
+  MSRowBwd p{dpx, x, lnw, lnb, mean, rstd, dg, g, gw, dion, SH, nx, mval, w2, cw, kv, m2, dx, dlnw, dlnb, dgw, dgb,
+             dSH, dmval, dw2, db2, dcw, dcb, db1, rows, ldsh, (int)M, (int)Dh, inv_sqrt_d, next_i, (int)layer, L,
+             gj, alpha, gm, ion, invL};
+  const size_t nb = next_i ? (size_t)(rows / L) : 0;  // + the next_i copy
+  const size_t shm = ((size_t)RW * (3 * d + M + 2 * Dh + 5) + nb) * sizeof(float);
+  ASRX_REQUIRE(shm <= 160 * 1024, "msheath_row_bwd2: %ld samples exceed the LDS budget", (long)nb);
+  MS_DISPATCH_MODE(2, row_grid(rows, 1024), shm, p);
+  ASRX_LAUNCHED("asrx_msheath_row_bwd2");
+}
+#undef MS_DISPATCH_MODE
 #undef MS_DISPATCH
 
 int asrx_tgate_fwd2(const float* G, const float* c, void* out, int out_bf16, int64_t rows, int64_t D,

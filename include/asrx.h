@@ -324,6 +324,7 @@ int asrx_msheath_row_fwd2(const float* x, const float* lnw, const float* lnb, co
  * (model.py:461) into xnew (when non-null) and its per-sample 64-row chunk column sums into part (B x
  * asrx_mem_chunks(L) x d, zeros for a sample not at the layer) -- asrx_axpy_row2_colsum's work in the same pass.
  * rows = B L. */
+/* (px may be NULL when xnew is given: no px store; the layer's backward then recomputes px.) */
 int asrx_msheath_row_fwd3(const float* x, const float* lnw, const float* lnb, const float* gw, const float* gb,
                           const float* SH, int64_t ldsh, const float* mval, const float* w2, const float* b2,
                           const float* cw, const float* cb, const float* tx, float* px, float* mean, float* rstd,
@@ -337,6 +338,19 @@ int asrx_msheath_row_bwd(const float* dpx, const float* x, const float* lnw, con
                          float* dgw, float* dgb, float* dSH, float* dmval, float* dw2, float* db2, float* dcw,
                          float* dcb, float* db1, int64_t rows, int64_t d, int64_t M, int64_t Dh, float inv_sqrt_d,
                          const float* next_i, int64_t layer, int64_t L, asrx_stream_t stream);
+/* asrx_msheath_row_bwd without the layer-sized passes that only carry g' = alpha[b] gj + gm[b, :] invL between
+ * kernels (gj: the gradient arriving at the layer's jump select; alpha (B), gm (B, d); rows = B L).  mode 2
+ * (update = px, no adapter): dx's base is formed per row, dx is only written (rows of samples at the layer); dpx,
+ * dg, dion unread (NULL); px is recomputed and t = g'.px, dion = g t, dg = ion t, dpx = g ion g' formed here
+ * (ion (rows) read).  mode 0: asrx_msheath_row_bwd.  There is no mode 1. */
+int asrx_msheath_row_bwd2(int mode, const float* gj, const float* alpha, const float* gm, float invL,
+                          const float* ion, const float* dpx, const float* x, const float* lnw, const float* lnb,
+                          const float* mean, const float* rstd, const float* dg, const float* g, const float* gw,
+                          const float* dion, const float* SH, int64_t ldsh, const float* nx, const float* mval,
+                          const float* w2, const float* cw, const float* kv, const float* m2, float* dx, float* dlnw,
+                          float* dlnb, float* dgw, float* dgb, float* dSH, float* dmval, float* dw2, float* db2,
+                          float* dcw, float* dcb, float* db1, int64_t rows, int64_t d, int64_t M, int64_t Dh,
+                          float inv_sqrt_d, const float* next_i, int64_t layer, int64_t L, asrx_stream_t stream);
 
 /* ---- tgate (model.py:532-535): G = sigmoid(x Wcat^T + b) (rows,3D) from asrx_gemm, c (rows,3). */
 int asrx_tgate_fwd(const float* G, const float* c, float* out, int64_t rows, int64_t D, asrx_stream_t stream);
@@ -423,6 +437,19 @@ int64_t asrx_jump_bwd_part_floats(int64_t B, int64_t L, int64_t d);
 int asrx_jump_select4_bwd_part(const float* g, const float* xn, const float* orig, const float* act,
                                const float* alpha, const float* beta, const int* has_orig, float* dxn, float* dorig,
                                float* dx, float* part, int64_t B, int64_t L, int64_t d, asrx_stream_t stream);
+/* The jump backward with dxn optional (NULL: alpha g is not stored; its consumers take g and alpha:
+ * asrx_axpy_row2_bwd_acc2, asrx_msheath_row_bwd2), partial-sum and atomic forms; and the x_new backward from
+ * (g, alpha) instead of dxn, writing dy, ds1, ds2 and dx = g' (adapter layers, ahead of asrx_msheath_row_bwd). */
+int asrx_jump_select4_bwd_part2(const float* g, const float* xn, const float* orig, const float* act,
+                                const float* alpha, const float* beta, const int* has_orig, float* dxn, float* dorig,
+                                float* dx, float* part, int64_t B, int64_t L, int64_t d, asrx_stream_t stream);
+int asrx_jump_select4_bwd_acc2(const float* g, const float* xn, const float* orig, const float* act,
+                               const float* alpha, const float* beta, const int* has_orig, float* dxn, float* dorig,
+                               float* dx, float* dalpha, float* dbeta, float* dgam, int64_t B, int64_t L, int64_t d,
+                               asrx_stream_t stream);
+int asrx_axpy_row2_bwd_acc2(const float* g, const float* alpha, const float* gm, float invL, const float* act,
+                            const float* s1, const float* s2, const float* y, float* dy, float* ds1, float* ds2,
+                            float* dx, int64_t B, int64_t L, int64_t d, asrx_stream_t stream);
 int asrx_msheath_ctrl_bwd4(const float* part, int64_t L, const float* g_mwo, const float* mem_v, const float* mem_w,
                            int64_t ld_mem_w, const float* mem, const float* jump_s, const void* rec, int64_t layer_i,
                            int64_t layers, int64_t B, int64_t D, float* g_policy, int acc_policy, float* g_mem_w,
@@ -668,6 +695,11 @@ int asrx_wgrad_bf16_ab(const void* A, int64_t lda, const void* B, int b_bf16, in
  * X fp32 (b_bf16 = 0) or bf16 (1), shapes as asrx_wgrad_bf16_ex / _ab. */
 int asrx_wgrad_bias(const void* A, int a_bf16, int64_t lda, const void* B, int b_bf16, int64_t ldb, float* C,
                     int64_t ldc, float* db, int64_t M, int64_t N, int64_t R, int64_t splitk, asrx_stream_t stream);
+/* asrx_wgrad_bf16_ex with two destinations: rows m < msplit of dY^T X are added into C (ldc), rows
+ * msplit <= m < M into C2 + (m - msplit) ldc2 -- two weight gradients sharing X in one pass over it. */
+int asrx_wgrad_split(const float* A, int64_t lda, const void* B, int b_bf16, int64_t ldb, float* C, int64_t ldc,
+                     float* C2, int64_t ldc2, int64_t msplit, int64_t M, int64_t N, int64_t R, int64_t splitk,
+                     asrx_stream_t stream);
 /* BatchNorm1d running statistics from per-clip (B, C) mean / rstd (ConvLite.bn, model.py:101);
  * nbt (num_batches_tracked, int64) may be NULL.  asrx_rsqrt_eps: eval-mode rstd. */
 int asrx_bn_running(const float* mean, const float* rstd, float* rm, float* rv, int64_t* nbt, int64_t B, int64_t C,
