@@ -197,6 +197,8 @@ SIGNATURES = {
     "asrx_gemm_wn_ce_f32": (_i32, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _i64, _i32, _p]),
     "asrx_ce_part_fwd": (_i32, [_p, _i64] + [_p] * 6 + [_i64, _i64, _p]),
     "asrx_ce_part_fwd_f32": (_i32, [_p, _i64] + [_p] * 6 + [_i64, _i64, _p]),
+    "asrx_gemm_wn_head": (_i32, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
+    "asrx_head_merge": (_i32, [_p, _i64] + [_p] * 8 + [_i64, _i64, _p]),
     "asrx_ce_bwd_bf16": (_i32, [_p] * 6 + [_i64, _i64, _p]),
     "asrx_ce_bwd_f32in": (_i32, [_p] * 6 + [_i64, _i64, _p]),
     "asrx_wgrad_bf16_ab": (_i32, [_p, _i64, _p, _i32, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p]),

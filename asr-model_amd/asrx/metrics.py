@@ -9,6 +9,8 @@ Same names, argument meaning and results as the reference:
   clean_ids / clean_batch                                        essentials.py:248-254
   setup_tokenizer(path) -> tokenizers.Tokenizer with the reference's encode/batch_decode/decode
                                                                  essentials.py:256-292
+  evaluate_loader(model, loader, tokenizer, generate=False)      essentials.py:875-935, on Model.evaluate:
+                                                                 ids and losses come back once per evaluation
 levenshtein keeps two DP rows instead of the reference's full matrix (same distance, O(n) memory).
 """
 from __future__ import annotations
@@ -98,6 +100,57 @@ def compute_metrics(pred, tokenizer=None, model=None, print_pred=False, num_samp
             if p.grad is not None:
                 result[f"per_layer_norms_{name}"] = float(p.grad.norm(2))
     return result
+
+
+def evaluate_loader(model, loader, tokenizer, generate=False):
+    """The reference's evaluation block (essentials.py:875-935) on Model.evaluate: per batch the teacher-forced
+    loss (893-903) and the predictions -- evaluate's argmax (918-920) or, with generate, the greedy decode
+    Model.generate(fused_head=True) (906-915).  Batches are dicts with text_ids, labels and any of spectrogram
+    / pitch / waveform.  Losses, counts and ids stay on the device while the loader runs and come to the host
+    in one transfer at the end.
+
+    -> {"loss": mean of the batch losses (0 without batches), "wer": compute_metrics' WER %, "samples",
+    "token_accuracy": teacher-forced predictions equal to their non-ignored label / non-ignored labels}.
+    The model is left in eval mode, as the reference leaves it."""
+    import torch
+
+    model.eval()
+    try:
+        dev = next(model.parameters()).device
+    except (AttributeError, StopIteration):
+        dev = None  # a model without parameters: tensors stay where the loader made them
+
+    def put(t):
+        return t if dev is None else t.to(dev)
+
+    stats, ids, shapes = [], [], []
+    samples = 0
+    for batch in loader:
+        feats = {k: put(batch[k]) for k in ("spectrogram", "pitch", "waveform") if batch.get(k) is not None}
+        text_ids = put(batch["text_ids"])
+        labels = put(batch["labels"].long())
+        samples += int(text_ids.shape[0])
+        out = model.evaluate(labels=labels, text_ids=text_ids, **feats)
+        pred = model.generate(max_new_tokens=labels.shape[1], fused_head=True, **feats) if generate \
+            else out["predictions"]
+        stats.append(torch.stack([out[k].reshape(()).double() for k in ("loss", "correct", "count")]))
+        ids += [pred.reshape(-1).double(), labels.reshape(-1).double()]  # ids < 2^53: exact
+        shapes.append((tuple(pred.shape), tuple(labels.shape)))
+    if not stats:
+        return {"loss": 0.0, "wer": 0.0, "samples": 0, "token_accuracy": 0.0}
+    flat = torch.cat([torch.stack(stats).reshape(-1)] + ids).cpu()  # the one transfer
+    nb = len(stats)
+    st = flat[:3 * nb].view(nb, 3)
+    all_p, all_l, o = [], [], 3 * nb
+    for ps, ls in shapes:
+        for rows, cols, dst in ((ps[0], ps[1], all_p), (ls[0], ls[1], all_l)):
+            dst.extend(flat[o:o + rows * cols].view(rows, cols).long().tolist())
+            o += rows * cols
+    wer = compute_metrics({"predictions": np.array(all_p, dtype=object), "label_ids": np.array(all_l, dtype=object)},
+                          tokenizer=tokenizer)["wer"]
+    count = float(st[:, 2].sum())
+    return {"loss": float(st[:, 0].sum()) / nb, "wer": wer, "samples": samples,
+            "token_accuracy": float(st[:, 1].sum()) / count if count > 0 else 0.0}
 
 
 def setup_tokenizer(path: str):

@@ -770,6 +770,21 @@ class processor(nn.Module):  # noqa: N801  (model.py:585-629)
         out = self.ln.run(g.contiguous(), noise, "final.ln", 0, T, out_bf16=True)
         return ops.linear(out, self.token.weight)
 
+    def decode_features(self, x, kv, noise: NoiseCtx):
+        """decode_logits up to and including the final norm over all prefix rows (B, T, D): the input of
+        ops.logits_head for generate(fused_head=True)."""
+        B, T = x.shape
+        i = len(self.block) - 1
+        blk = self.block[i]
+        h = ops.add_rows(ops.Embedding.apply(x, self.token.weight), self.position)
+        a = blk.call(h, noise, f"b{i}.ta", 0, masked=True)
+        b_ = blk.call(a, noise, f"b{i}.tb", 0, kv=kv[0])
+        c_ = blk.call(b_, noise, f"b{i}.tc", 0, kv=kv[1])
+        d = blk.call(c_, noise, f"b{i}.td", 0, kv=kv[2])
+        e = ops.add(a, b_, c_)
+        g = blk.call(d, noise, f"b{i}.tg", 0, kv=blk.xa_side(e, noise, f"b{i}.tg.xa", 0))
+        return self.ln.run(g.contiguous(), noise, "final.ln", 0, T, out_bf16=True)
+
     @staticmethod
     def _audio(blk, streams, noise, site, B, kind):
         """Run blk.call / blk.xa_side on the 3 audio streams, batching streams of equal length."""
@@ -882,6 +897,38 @@ class Model(nn.Module):
         self._end_step_after(logits, loss)
         return {"logits": logits, "loss": loss}
 
+    @torch.no_grad()
+    def evaluate(self, labels, text_ids, spectrogram=None, pitch=None, waveform=None):
+        """The teacher-forced evaluation pass (essentials.py:893-920: model(...)["loss"] and
+        torch.argmax(output["logits"], -1)) without the logits: forward's stream selection, noise context,
+        grad_signature and switches (skip_dead_blocks, fused_ce, the precision mode), then ops.logits_head on
+        the final norm's output.  -> {"loss", "predictions" (B, T) int64, "correct" (labels != 0 predicted
+        right), "count" (labels != 0), "logits": None}, all on the device: no host
+        synchronisation.  The mode (train / eval) is the caller's, as with forward; the step ends here."""
+        first = next((t for t in (pitch, spectrogram, waveform) if t is not None), None)
+        if first is None or text_ids is None or labels is None:
+            raise ValueError("evaluate needs labels, text_ids and at least one of pitch/spectrogram/waveform")
+
+        def aborc(a, b, c):  # essentials.py:25
+            return a if a is not None else (b if b is not None else c)
+
+        streams = [aborc(pitch, spectrogram, waveform), aborc(spectrogram, pitch, waveform),
+                   aborc(waveform, pitch, spectrogram)]
+        streams = [s.to(torch.float32) for s in streams]
+        B = first.shape[0]
+        self.grad_signature = (self.training, stream_grouping([s.shape[-1] for s in streams]))
+        gemm_mod.clear_weight_cache(self)
+        noise = NoiseCtx(self.noise_seed, self.noise_step, self.training)
+        if self.training:
+            self.noise_step += 1
+        enc = self.enc.encode(streams, noise, B)
+        xa = {"a": enc[0], "b": enc[1], "c": enc[2]}
+        h = self.processor(text_ids, xa, noise, seq=False, features=True)
+        out = ops.logits_head(h, self.processor.token.weight, labels, fused=self.fused_ce)
+        self._end_step()
+        return {"loss": out["loss"], "predictions": out["pred"], "correct": out["correct"], "count": out["count"],
+                "logits": None}
+
     def _end_step(self):
         """End of a step: join the dead blocks' side streams, drop the per-step weight copies."""
         self.processor.join_dead_blocks()
@@ -914,7 +961,8 @@ class Model(nn.Module):
             t.register_hook(hook)
 
     @torch.no_grad()
-    def generate(self, spectrogram=None, pitch=None, waveform=None, pitch_tokens=None, max_new_tokens=150):
+    def generate(self, spectrogram=None, pitch=None, waveform=None, pitch_tokens=None, max_new_tokens=150,
+                 fused_head=False):
         """Greedy decoding, model.py:674-701: the encoder once, then per new token the processor with
         seq=True on the tokens so far (BOS = 1 first), argmax of the last position, stop when every
         sequence emitted EOS = 2.  Returns LongTensor (B, <= 1 + max_new_tokens).
@@ -925,7 +973,11 @@ class Model(nn.Module):
         text-side KV cache would change the result.  What is y-independent is cached: the audio
         self-calls and the cross-attention k/v of the live block (processor.audio_cache).  The
         gumbel noise is the model's keyed noise at one (seed, step), the same for every decoding
-        step (the reference draws fresh noise per call: its decoding is not reproducible)."""
+        step (the reference draws fresh noise per call: its decoding is not reproducible).
+
+        fused_head: the processor runs as above up to the final norm over every prefix row (its keyed noise is
+        indexed by position), then ops.logits_head takes the argmax of the B last-position rows only, read
+        through a strided view -- no logits of the earlier positions, no (B, T, V) tensor."""
         if pitch_tokens is not None:
             raise NotImplementedError("pitch_tokens: see Model.forward")
         self.eval()
@@ -946,8 +998,12 @@ class Model(nn.Module):
         kv = self.processor.audio_cache({"a": enc[0], "b": enc[1], "c": enc[2]}, noise, B)
         y = torch.ones(B, 1, dtype=torch.long, device=first.device)
         for _ in range(max_new_tokens):
-            logits = self.processor.decode_logits(y, kv, noise)
-            nxt = torch.argmax(logits[:, -1, :], dim=-1, keepdim=True)
+            if fused_head:
+                h = self.processor.decode_features(y, kv, noise)
+                nxt = ops.logits_head(h[:, -1], self.processor.token.weight)["pred"].unsqueeze(1)
+            else:
+                logits = self.processor.decode_logits(y, kv, noise)
+                nxt = torch.argmax(logits[:, -1, :], dim=-1, keepdim=True)
             y = torch.cat((y, nxt), dim=1)
             if bool((nxt == 2).all()):
                 break

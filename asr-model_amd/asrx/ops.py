@@ -1989,6 +1989,70 @@ def logits_ce(h, W, labels, bf16_logits=False):
     return LogitsCE.apply(h, W, labels, sink_of(h), bool(bf16_logits))
 
 
+def logits_head(h, W, labels=None, nj=None, fused=True):
+    """The tied-logits head without the logits (essentials.py:893-920 evaluation, model.py:691-699 the greedy
+    step): a dict of device tensors -- pred (h's leading dims, int64) = argmax(h W^T, -1) with torch.argmax's
+    lowest-index tie rule, and with labels also loss (F.cross_entropy(., labels, ignore_index=0), NaN when
+    every label is ignored or one is outside [0, V)), loss_rows and lse (leading dims, fp32), count (the
+    rows with label != 0; fp32 ()) and correct (rows with label != 0 and pred == label; int64 ()).
+
+    Where logits_ce_ok(h, W) holds (and fused) the GEMM keeps each output tile on chip and writes per-tile
+    (max, sum exp, argmax) partials (asrx_gemm_wn_head + asrx_head_merge): no (rows, V) tensor exists.  h may
+    be a 2-D view with a row stride (the last position of each sample).  Elsewhere -- fp32 parity mode, shapes
+    the fused kernel does not take, fused=False -- the same dict comes from ops.linear, the one-pass cross
+    entropy and torch.argmax.  nj: the tile width 128 * nj (default: LogitsCE's); tests reach every width.
+    Not differentiable."""
+    if _grad_needed(h, W):
+        raise RuntimeError("ops.logits_head is not differentiable: call it under torch.no_grad() (training "
+                           "takes ops.logits_ce)")
+    lib.require_gpu(h, W, labels)
+    V, D = W.shape[0], h.shape[-1]
+    lead = h.shape[:-1]
+    lab = None if labels is None else _c(labels.reshape(-1))
+    if lab is not None and (lab.numel() != h.numel() // D or lab.dtype != torch.int64):
+        raise ValueError("ops.logits_head: labels must be int64, one per row of h")
+    dev = h.device
+    if fused and logits_ce_ok(h, W):
+        if h.dim() == 2 and h.stride(1) == 1 and h.stride(0) >= D and h.stride(0) % 8 == 0:
+            lda = h.stride(0)  # a strided row view is read in place
+        else:
+            h, lda = _c(h), D
+        rows = h.numel() // D
+        pred = _E(lead, dtype=torch.int64, device=dev)
+        nj = G._nj(rows, V) if nj is None else int(nj)
+        nparts = (V + 128 * nj - 1) // (128 * nj)
+        part = _E(3, rows, nparts, device=dev)  # (max, sum exp) pairs, then the int32 columns
+        out = {"pred": pred}
+        zlab = loss_r = lse = loss = count = correct = None
+        if lab is not None:
+            zlab, loss_r, lse = _E(rows, device=dev), _E(lead, device=dev), _E(lead, device=dev)
+            loss, count = _E((), device=dev), _E((), device=dev)
+            correct = _E((), dtype=torch.int64, device=dev)
+            out.update(loss=loss, loss_rows=loss_r, lse=lse, count=count, correct=correct)
+        Wb = G.weight_bf16(W)
+        e0 = probe.begin("gemm")
+        lib.call("asrx_gemm_wn_head", _P(h), lda, _P(Wb), Wb.stride(0), _P(part), _P(lab), _P(zlab), rows, V, D, nj,
+                 _S())
+        probe.end("gemm", e0, 2.0 * rows * V * D, ("head", rows, V, D, nj))
+        lib.call("asrx_head_merge", _P(part), nparts, _P(zlab), _P(lab), _P(pred), _P(loss_r), _P(lse), _P(loss),
+                 _P(count), _P(correct), rows, V, _S())
+        return out
+    logits = linear(h, W)
+    rows = logits.numel() // V
+    pred = torch.argmax(logits, dim=-1)
+    out = {"pred": pred}
+    if lab is not None:
+        z = _c(logits.float())
+        loss_r, lse = _E(lead, device=dev), _E(lead, device=dev)
+        loss = _E((), device=dev)
+        lib.call("asrx_ce_fwd1", _P(z), _P(lab), _P(loss_r), _P(lse), _P(loss), _P(_E(1, device=dev)), rows, V, _S())
+        live = lab != 0
+        count = live.sum().to(torch.float32)
+        correct = ((pred.reshape(-1) == lab) & live).sum()
+        out.update(loss=loss, loss_rows=loss_r, lse=lse, count=count, correct=correct)
+    return out
+
+
 class BlendFn(torch.autograd.Function):
     """sigmoid(blend) d + (1 - sigmoid(blend)) g (processor output, model.py:628)."""
 

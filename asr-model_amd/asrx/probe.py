@@ -94,7 +94,7 @@ def _rows_of(M, rl):
 
 def gemm_wr_bytes(tag):
     """Algorithmic HBM bytes of one gemm_wr_kernel launch (every instantiation: plain / residual / tied
-    logits, router, activation-gradient) from its probe tag; None for the other GEMM kernels.  Counted once
+    logits, logits-free head, router, activation-gradient) from its probe tag; None for the other GEMM kernels.  Counted once
     each: A (4 B fp32 or 2 B bf16-stored per element; a k3 conv's implicit im2col reads each activation row
     once, so K/3 of it), the bf16 weight (2 N K), C written (4 / 2 B), C or the residual read again
     (beta / RES), the saved fp32 pre-activation; router: logits 3 x 4 B per row (+ h_pre when kept);
@@ -114,6 +114,9 @@ def gemm_wr_bytes(tag):
     if kind == "gact":
         _, M, N, K, _nj, _act, ab = tag
         return (2 if ab else 4) * M * K + 2 * N * K + 6 * M * N
+    if kind == "head":  # logits-free head: no C; 12 B of partials per row and column tile
+        _, M, N, K, nj = tag
+        return 2 * M * K + 2 * N * K + 12 * M * ((N + 128 * nj - 1) // (128 * nj))
     return None
 
 

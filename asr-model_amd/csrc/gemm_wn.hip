@@ -212,6 +212,36 @@ extern "C" int asrx_gemm_wn_ce_f32(const void* A, int64_t lda, const unsigned sh
   ASRX_LAUNCHED("asrx_gemm_wn_ce_f32");
 }
 
+// Logits-free head (essentials.py:875-935 evaluation: model(...)["loss"] and torch.argmax(logits, -1);
+// model.py:691-699 the greedy step's argmax): the tied-logits product of asrx_gemm_wn_ce_f32 without the
+// logits store.  part: M x nparts float2 (max, sum exp(z - max)) of each 128*nj-column tile's fp32 logits --
+// the numbers asrx_gemm_wn_ce_f32 writes -- followed by M x nparts int32, the column of that max (the lowest
+// among equal maxima; INT_MAX for a tile without a value above -inf).  labels (nullable, int64 per row): the
+// logit of each row's label goes to zlab[row]; label 0 and labels outside [0, N) write nothing.  lda may
+// exceed K (the last position of each sample through a strided view).  asrx_head_merge finishes the rows.
+extern "C" int asrx_gemm_wn_head(const void* A, int64_t lda, const unsigned short* W, int64_t ldw, float* part,
+                                 const int64_t* labels, float* zlab, int64_t M, int64_t N, int64_t K, int nj,
+                                 hipStream_t stream) {
+  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_head: empty problem");
+  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)part & 7) == 0,
+               "asrx_gemm_wn_head: A/W 16-byte, part 8-byte aligned");
+  ASRX_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && N % 4 == 0 && lda >= K,
+               "asrx_gemm_wn_head: K, lda, ldw %% 8, N %% 4 and lda >= K required");
+  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_head: operand spans >= 2^31 elements");
+  ASRX_REQUIRE(nj >= 1 && nj <= 3, "asrx_gemm_wn_head: nj in 1..3");
+  ASRX_REQUIRE(!labels || zlab, "asrx_gemm_wn_head: labels need zlab");
+  const int64_t nparts = (N + 128 * nj - 1) / (128 * nj);
+  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, nullptr, (int)N, nullptr, nullptr, (int)M, (int)N, (int)K,
+               1, 1, 1.f, 0.f, ACT_NONE, nullptr, nullptr, nullptr, nullptr, nullptr, (float2*)part, (int)nparts};
+  p.hd_idx = reinterpret_cast<int*>(part + 2 * M * nparts);
+  p.hd_labels = labels;
+  p.hd_zlab = zlab;
+  if (nj == 3) wn::launch_wr<3, false, false, true, true, false, false, false, true>(p, stream);
+  else if (nj == 2) wn::launch_wr<2, false, false, true, true, false, false, false, true>(p, stream);
+  else wn::launch_wr<1, false, false, true, true, false, false, false, true>(p, stream);
+  ASRX_LAUNCHED("asrx_gemm_wn_head");
+}
+
 // Out projection with its residual add (model.py:578-580 x = x + attn(...).out): C = R + A W^T + bias, A, C
 // and R fp32 (R may not alias C), 16-byte aligned rows; nj 1 or 3 (the residual epilogue is compiled into
 // dedicated instantiations only, so the other GEMMs keep their register budget).

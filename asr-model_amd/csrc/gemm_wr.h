@@ -82,6 +82,13 @@ struct Params {
   const float2* rot_tab;
   int rot_L, rot_half;
   float rot_scale;
+  // logits-free head (gemm_wr_kernel<..., CE, HEAD>; essentials.py:875-935 evaluation, model.py:691-699 greedy
+  // step): no logits are stored -- per row and BN-column tile the (max, sum exp(z - max)) of the tile's fp32
+  // logits go to ce_part as in the CE variant and the column of that max (lowest among equals) to
+  // hd_idx[row * ce_ld + tile]; with hd_labels (nullable) the logit of each row's label goes to hd_zlab[row]
+  int* hd_idx;
+  const int64_t* hd_labels;
+  float* hd_zlab;
 };
 
 __device__ __forceinline__ void st_bf16x4(unsigned short* dst, float a, float b, float c, float d) {
@@ -411,6 +418,94 @@ __device__ __forceinline__ void epilogue_ce(const Params& p, f32x4 (&acc)[4][2 *
         m = mn;
       }
       p.ce_part[(int64_t)row * p.ce_ld + n0 / Cfg<NJ>::BN] = make_float2(m, sm);
+    }
+  }
+}
+
+// Logits-free head epilogue (Params::hd_idx): epilogue_ce's slab and its (max, sum exp) of the fp32 values --
+// the same numbers asrx_gemm_wn_ce_f32 reduces -- without the logits store, plus the column of the max.  Among
+// equal maxima the lowest column wins at every level (torch.argmax's rule): a lane scans its quarter in
+// ascending columns and replaces only on a strictly greater value, the merges over the row's 4 lanes and over
+// the 4 column waves (redi: BM x 4 int beside red) prefer the lower column on equality.  A quarter / tile
+// without a finite value keeps column INT_MAX (asrx_head_merge turns a row of those into column 0).
+// labs: this tile's labels (BM int, staged with the tile's first k-step; -1 = none, ignored or outside
+// [0, N)): the lane whose quarter holds column labs[row] writes that logit to hd_zlab[row].
+__device__ __forceinline__ void head_pick(float& m, int& ix, float mo, int io) {
+  if (mo > m || (mo == m && io < ix)) ix = io;
+}
+template <int NJ>
+__device__ __forceinline__ void epilogue_head(const Params& p, f32x4 (&acc)[4][2 * NJ], int m0, int n0, int wm, int wn,
+                                              int lr, int lk, float* ep, float2* red, int* redi, const int* labs) {
+  constexpr int NT = 2 * NJ, W = EpLds<NJ>::W, LD = EpLds<NJ>::LD, Q = W / 4;
+  constexpr int NONE = 0x7fffffff;
+  const int lane = threadIdx.x & 63;
+  const int cbase = n0 + wn * W;
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int nl = nt * 16 + 4 * lk;
+      *reinterpret_cast<float4*>(ep + lr * LD + nl) =
+          make_float4(p.alpha * acc[mt][nt][0], p.alpha * acc[mt][nt][1], p.alpha * acc[mt][nt][2],
+                      p.alpha * acc[mt][nt][3]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    {
+      const int rr = lane >> 2, q = lane & 3;
+      const int rl = wm * 64 + mt * 16 + rr;
+      const float* src = ep + rr * LD + q * Q;
+      const int c0 = cbase + q * Q;
+      float m = -INFINITY;
+      int ix = NONE;
+#pragma unroll
+      for (int i = 0; i < Q; ++i)
+        if (c0 + i < p.N) {
+          if (src[i] > m) ix = c0 + i;
+          m = fmaxf(m, src[i]);
+        }
+      float sm = 0.f;
+      if (m != -INFINITY) {
+#pragma unroll
+        for (int i = 0; i < Q; ++i)
+          if (c0 + i < p.N) sm += __expf(src[i] - m);
+      }
+      const int y = labs[rl];  // < N, so inside the tile's valid columns when inside the quarter
+      if (y >= c0 && y < c0 + Q && m0 + rl < p.M) p.hd_zlab[m0 + rl] = src[y - c0];
+#pragma unroll
+      for (int o = 1; o <= 2; o <<= 1) {
+        const float mo = __shfl_xor(m, o), so = __shfl_xor(sm, o);
+        const int io = __shfl_xor(ix, o);
+        head_pick(m, ix, mo, io);
+        const float mn = fmaxf(m, mo);
+        sm = (m == -INFINITY ? 0.f : sm * __expf(m - mn)) + (mo == -INFINITY ? 0.f : so * __expf(mo - mn));
+        m = mn;
+      }
+      if (q == 0) {
+        red[rl * 4 + wn] = make_float2(m, sm);
+        redi[rl * 4 + wn] = ix;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the next slice overwrites the slab
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // as epilogue_ce: no vmcnt(0) fence
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  if (threadIdx.x < BM) {
+    const int row = m0 + threadIdx.x;
+    if (row < p.M) {
+      float m = -INFINITY, sm = 0.f;
+      int ix = NONE;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float2 v = red[threadIdx.x * 4 + w];
+        head_pick(m, ix, v.x, redi[threadIdx.x * 4 + w]);
+        const float mn = fmaxf(m, v.x);
+        sm = (m == -INFINITY ? 0.f : sm * __expf(m - mn)) + (v.x == -INFINITY ? 0.f : v.y * __expf(v.x - mn));
+        m = mn;
+      }
+      const int64_t o = (int64_t)row * p.ce_ld + n0 / Cfg<NJ>::BN;
+      p.ce_part[o] = make_float2(m, sm);
+      p.hd_idx[o] = ix;
     }
   }
 }
@@ -756,8 +851,9 @@ __device__ __forceinline__ void wr_load64_fast(const Params& p, WrStage64<ABF>& 
 }
 
 template <int NJ, bool CONV, bool RT, int DEP = 0, bool ABF = false, bool CE = false, bool RES = false,
-          bool GA = false, bool ROT = false>
+          bool GA = false, bool ROT = false, bool HEAD = false>
 __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) {  // ntiles: all tiles
+  static_assert(!HEAD || (CE && ABF), "the head epilogue is a variant of the bf16-A CE instantiation");
   typedef Cfg<NJ> CF;
   constexpr int BN = CF::BN, NT = 2 * NJ, BNR = CF::BNR;
   constexpr bool K64 = NJ == 1 && !CONV;  // 64-deep k-steps (WrStage64)
@@ -769,6 +865,8 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) 
   __shared__ __attribute__((aligned(16))) float bias_s[2][BNR];
   __shared__ float w2s[RT ? 3 * BN : 1];
   __shared__ __attribute__((aligned(16))) float red[RT ? BM * 12 : (CE ? BM * 8 : 1)];
+  __shared__ int redi[HEAD ? BM * 4 : 1];   // head: the column waves' argmax partials, beside red
+  __shared__ int lab_s[HEAD ? 2 * BM : 1];  // head: the tile's labels, double-buffered like bias_s
   __shared__ __attribute__((aligned(16))) float ep_s[RT ? 1 : 8 * EpLds<NJ>::FLOATS];
   if constexpr (RT) {
     for (int i = threadIdx.x; i < 3 * BN; i += NTHR) {
@@ -857,7 +955,14 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) 
   auto store = [&](int s, const Stg& st) __attribute__((always_inline)) {
     if constexpr (K64) wr_store64<ABF>(st, a_img[s & 1], b_img[s & 1]);
     else wr_store<NJ, ABF>(st, a_img[s & 1], b_img[s & 1]);
-    if (cs.kk == 0) {  // first k-step of a tile: its bias slice (read by the tile's epilogue)
+    if constexpr (HEAD) {
+      if (cs.kk == 0 && threadIdx.x < BM) {  // first k-step of a tile: its rows' labels (no bias)
+        const int row = cs.m0 + threadIdx.x;
+        int64_t y = -1;
+        if (p.hd_labels && row < p.M) y = p.hd_labels[row];
+        lab_s[(cs.j & 1) * BM + threadIdx.x] = (y > 0 && y < p.N) ? (int)y : -1;
+      }
+    } else if (cs.kk == 0) {  // first k-step of a tile: its bias slice (read by the tile's epilogue)
       float* dst = bias_s[cs.j & 1];
       for (int c = threadIdx.x; c < BN; c += NTHR) dst[c] = (p.bias && cs.n0 + c < p.N) ? p.bias[cs.n0 + c] : 0.f;
     }
@@ -948,6 +1053,9 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) 
 #endif
       if constexpr (RT) {
         epilogue_router<NJ>(p, acc, bsl, w2s, red, m0, wm, wn, lr, lk);
+      } else if constexpr (HEAD) {
+        epilogue_head<NJ>(p, acc, m0, n0, wm, wn, lr, lk, ep, reinterpret_cast<float2*>(red), redi,
+                          lab_s + (ce.j & 1) * BM);
       } else if constexpr (CE) {
         epilogue_ce<NJ>(p, acc, m0, n0, wm, wn, lr, lk, ep, reinterpret_cast<float2*>(red));
       } else if constexpr (RES) {  // act none, vec_ok (checked by the launcher)
@@ -1010,10 +1118,10 @@ template <bool ABF>
 constexpr int wr_dep() { return 0; }
 
 template <int NJ, bool CONV, bool RT = false, bool ABF = false, bool CE = false, bool RES = false, bool GA = false,
-          bool ROT = false>
+          bool ROT = false, bool HEAD = false>
 void launch_wr(const Params& p, hipStream_t s) {
   static int resident = 0;
-  const void* fn = (const void*)gemm_wr_kernel<NJ, CONV, RT, wr_dep<ABF>(), ABF, CE, RES, GA, ROT>;
+  const void* fn = (const void*)gemm_wr_kernel<NJ, CONV, RT, wr_dep<ABF>(), ABF, CE, RES, GA, ROT, HEAD>;
   if (!resident) {
     int per_cu = 0, dev = 0, cus = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NTHR, 0);
@@ -1025,7 +1133,7 @@ void launch_wr(const Params& p, hipStream_t s) {
   const int grid = std::min(tiles, resident);
   // a 5-deep pipeline (DEP = 5) for the one-wave 8192-row text-side launches measured 32.4 us vs
   // 30.1 us at depth 3 (profiles/r02_bench_v8_kernel_stats.csv): their time is not load latency
-  gemm_wr_kernel<NJ, CONV, RT, wr_dep<ABF>(), ABF, CE, RES, GA, ROT><<<grid, NTHR, 0, s>>>(p, tiles);
+  gemm_wr_kernel<NJ, CONV, RT, wr_dep<ABF>(), ABF, CE, RES, GA, ROT, HEAD><<<grid, NTHR, 0, s>>>(p, tiles);
 }
 
 }  // namespace wn
@@ -1039,12 +1147,14 @@ void launch_wr(const Params& p, hipStream_t s) {
 #define ASRX_WR_DECL_RES(NJ) extern template void asrx::wn::launch_wr<NJ, false, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
 #define ASRX_WR_DECL_GA(NJ, ABF) extern template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, true>(const asrx::wn::Params&, hipStream_t);
 #define ASRX_WR_DECL_ROT(NJ, ABF) extern template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
+#define ASRX_WR_DECL_HEAD(NJ) extern template void asrx::wn::launch_wr<NJ, false, false, true, true, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
 #else
 #define ASRX_WR_DECL(NJ, CONV, RT, ABF) template void asrx::wn::launch_wr<NJ, CONV, RT, ABF>(const asrx::wn::Params&, hipStream_t);
 #define ASRX_WR_DECL_CE(NJ) template void asrx::wn::launch_wr<NJ, false, false, true, true>(const asrx::wn::Params&, hipStream_t);
 #define ASRX_WR_DECL_RES(NJ) template void asrx::wn::launch_wr<NJ, false, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
 #define ASRX_WR_DECL_GA(NJ, ABF) template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, true>(const asrx::wn::Params&, hipStream_t);
 #define ASRX_WR_DECL_ROT(NJ, ABF) template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
+#define ASRX_WR_DECL_HEAD(NJ) template void asrx::wn::launch_wr<NJ, false, false, true, true, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
 #endif
 #define ASRX_WR_SET(NJ) ASRX_WR_DECL(NJ, false, false, false) ASRX_WR_DECL(NJ, true, false, false) \
   ASRX_WR_DECL(NJ, false, false, true) ASRX_WR_DECL(NJ, true, false, true) ASRX_WR_DECL(NJ, false, true, false)
@@ -1063,4 +1173,7 @@ ASRX_WR_DECL_ROT(1, true)
 ASRX_WR_DECL_ROT(1, false)
 ASRX_WR_DECL_ROT(3, true)
 ASRX_WR_DECL_ROT(3, false)
+ASRX_WR_DECL_HEAD(1)
+ASRX_WR_DECL_HEAD(2)
+ASRX_WR_DECL_HEAD(3)
 #endif

@@ -93,6 +93,84 @@ __global__ __launch_bounds__(256) void ce_part_fwd_kernel(const float2* __restri
   }
 }
 
+// The rows of the logits-free head (asrx_gemm_wn_head) from its per-tile partials: the (max, sum exp) pairs
+// merge in ce_part_fwd_kernel's order, so lse is the number the fused cross entropy gives; pred is the column
+// of the global max, the lowest among the tiles (and, within one, the columns) that hold it -- torch.argmax's
+// rule; column 0 when no tile has a value above -inf.  With labels: loss_r = lse - zlab (0 for label 0, NaN
+// for a label outside [0, V)).  labels null: pred only (the decode form).  One wave per row.
+__global__ __launch_bounds__(256) void head_merge_kernel(const float2* __restrict__ part, const int* __restrict__ idx,
+                                                         int nparts, const float* __restrict__ zlab,
+                                                         const int64_t* __restrict__ labels, int64_t* __restrict__ pred,
+                                                         float* __restrict__ loss, float* __restrict__ lse, int64_t rows,
+                                                         int64_t V) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= rows) return;
+  float m = -INFINITY, s = 0.f;
+  int ix = 0x7fffffff;
+  for (int j = lane; j < nparts; j += 64) {
+    const float2 v = part[r * nparts + j];
+    const int iv = idx[r * nparts + j];
+    if (v.x > m || (v.x == m && iv < ix)) ix = iv;
+    const float mn = fmaxf(m, v.x);
+    s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (v.x == -INFINITY ? 0.f : v.y * __expf(v.x - mn));
+    m = mn;
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float mo = __shfl_xor(m, o), so = __shfl_xor(s, o);
+    const int io = __shfl_xor(ix, o);
+    if (mo > m || (mo == m && io < ix)) ix = io;
+    const float mn = fmaxf(m, mo);
+    s = (m == -INFINITY ? 0.f : s * __expf(m - mn)) + (mo == -INFINITY ? 0.f : so * __expf(mo - mn));
+    m = mn;
+  }
+  if (lane == 0) {
+    pred[r] = (ix >= 0 && ix < V) ? ix : 0;
+    if (labels) {
+      const int64_t y = labels[r];
+      const float l = m + logf(s);
+      lse[r] = l;
+      float lr = 0.f;
+      if (y < 0 || y >= V) lr = __builtin_nanf("");
+      else if (y != 0) lr = l - zlab[r];
+      loss[r] = lr;
+    }
+  }
+}
+
+// correct = #{rows: label != 0 and pred == label} and count = #{rows: label != 0} (numerator and denominator of
+// asrx.metrics.evaluate_loader's token accuracy): integer partial counts summed by one workgroup in a fixed
+// order.  count replaces ce_reduce_kernel's max(#, 1) -- a backward's divisor, which evaluation has no use for.
+__global__ __launch_bounds__(1024) void head_count_kernel(const int64_t* __restrict__ pred,
+                                                          const int64_t* __restrict__ labels, int64_t rows,
+                                                          int64_t* __restrict__ correct, float* __restrict__ count) {
+  __shared__ int red[2][16];
+  int c = 0, n = 0;
+  for (int64_t r = threadIdx.x; r < rows; r += 1024) {
+    const int64_t y = labels[r];
+    n += y != 0 ? 1 : 0;
+    c += (y != 0 && pred[r] == y) ? 1 : 0;
+  }
+  for (int o = 32; o >= 1; o >>= 1) {
+    c += __shfl_xor(c, o);
+    n += __shfl_xor(n, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = c;
+    red[1][threadIdx.x >> 6] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t tc = 0, tn = 0;
+    for (int i = 0; i < 16; ++i) {
+      tc += red[0][i];
+      tn += red[1][i];
+    }
+    correct[0] = tc;
+    count[0] = (float)tn;
+  }
+}
+
 // dz = (g / count) (softmax(z) - onehot(y)) from the bf16 logits, stored bf16 (it only feeds the two
 // gradient GEMMs, which round their operands to bf16 anyway).  One row per workgroup, 8 logits per
 // 16-byte load.
@@ -391,6 +469,23 @@ int asrx_ce_part_fwd_f32(const float* part, int64_t nparts, const float* zf, con
                                                                      labels, loss_r, lse, rows, V);
   ce_reduce_kernel<<<1, 1024, 0, stream>>>(loss_r, labels, rows, loss, count);
   ASRX_LAUNCHED("asrx_ce_part_fwd_f32");
+}
+
+int asrx_head_merge(const float* part, int64_t nparts, const float* zlab, const int64_t* labels, int64_t* pred,
+                    float* loss_r, float* lse, float* loss, float* count, int64_t* correct, int64_t rows, int64_t V,
+                    hipStream_t stream) {
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(nparts > 0 && rows < (1LL << 31) && V > 0 && V < (1LL << 31), "asrx_head_merge: bad shape");
+  ASRX_REQUIRE(((uintptr_t)part & 7) == 0 && pred, "asrx_head_merge: part 8-byte aligned, pred required");
+  ASRX_REQUIRE(!labels || (zlab && loss_r && lse && loss && count && correct),
+               "asrx_head_merge: labels need zlab, loss_r, lse, loss, count and correct");
+  head_merge_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, stream>>>(
+      (const float2*)part, (const int*)(part + 2 * rows * nparts), (int)nparts, zlab, labels, pred, loss_r, lse, rows, V);
+  if (labels) {
+    ce_reduce_kernel<<<1, 1024, 0, stream>>>(loss_r, labels, rows, loss, count);
+    head_count_kernel<<<1, 1024, 0, stream>>>(pred, labels, rows, correct, count);
+  }
+  ASRX_LAUNCHED("asrx_head_merge");
 }
 
 int asrx_ce_bwd_f32in(const float* zf, const int64_t* labels, const float* lse, const float* g, const float* count,

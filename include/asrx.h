@@ -652,6 +652,28 @@ int asrx_ce_part_fwd_f32(const float* part, int64_t nparts, const float* zf, con
                          float* lse, float* loss, float* count, int64_t rows, int64_t V, asrx_stream_t stream);
 int asrx_ce_bwd_f32in(const float* zf, const int64_t* labels, const float* lse, const float* g, const float* count,
                       unsigned short* dzb, int64_t rows, int64_t V, asrx_stream_t stream);
+/* Logits-free head: evaluation and the greedy step want one token id per row and one loss per batch, not the
+ * logits.  asrx_gemm_wn_head (csrc/gemm_wn.hip) is asrx_gemm_wn_ce_f32's product without the logits store: part
+ * receives rows x nparts float2 (max, sum exp(z - max)) of each 128*nj-column tile's fp32 logits -- the numbers
+ * asrx_gemm_wn_ce_f32 writes -- followed by rows x nparts int32, the column of that max (lowest column among
+ * equal maxima, torch.argmax's rule; nparts = ceil(N / (128 nj)), so part holds 3 * rows * nparts 4-byte
+ * words); with labels (nullable) the logit of each row's label goes to zlab[row] (label 0 and labels outside
+ * [0, N) write nothing).  A bf16 (M x K, lda >= K: decode passes the last position of each sample through a
+ * strided view), W bf16 (N x K).  Replaces model.py:629 logits = x @ token.weight^T where only their argmax and
+ * loss are used: essentials.py:893-903 and 918-920 (model(...)["loss"], torch.argmax(output["logits"], -1)) and
+ * model.py:691-699 (generate's argmax of the last position). */
+int asrx_gemm_wn_head(const void* A, int64_t lda, const unsigned short* W, int64_t ldw, float* part,
+                      const int64_t* labels, float* zlab, int64_t M, int64_t N, int64_t K, int nj,
+                      asrx_stream_t stream);
+/* asrx_head_merge (csrc/stepops.hip) finishes the rows from those partials: pred[row] (int64) = the column of the
+ * row's maximum (0 for a row without a value above -inf), and with labels lse[row], loss_r[row] = lse - zlab (0
+ * for label 0, NaN for a label outside [0, V)), loss = sum loss_r / #{labels != 0} (NaN when every label is
+ * ignored) as asrx_ce_part_fwd_f32, count = # (fp32; 0 when every label is ignored -- not the backward's divisor
+ * max(#, 1)) and correct (int64) = #{label != 0 and pred == label}, integer sums in a fixed order.  labels NULL: pred only (zlab .. correct unused).  Replaces F.cross_entropy
+ * (model.py:670) and torch.argmax (essentials.py:919, model.py:695) over stored logits. */
+int asrx_head_merge(const float* part, int64_t nparts, const float* zlab, const int64_t* labels, int64_t* pred,
+                    float* loss_r, float* lse, float* loss, float* count, int64_t* correct, int64_t rows, int64_t V,
+                    asrx_stream_t stream);
 /* out projection with its residual add (model.py:578-580): C = R + A W^T + bias; A, C, R fp32, R != C,
  * 16-byte aligned rows, nj 1 or 3. */
 /* Backward of y = act(A W^T + bias), act gelu (1) / silu (2) / sigmoid (3), whose forward kept no pre-activation:
