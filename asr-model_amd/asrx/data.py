@@ -143,10 +143,16 @@ class prepare_datasets(torch.utils.data.Dataset):  # noqa: N801  (reference clas
 
 
 def extract_features_batch(batches, tokenizer=None, spectrogram=False, waveform=False, pitch=False, phase=False,
-                           hop_length=160, sample_rate=16000, mels=128, **unsupported):
+                           hop_length=160, sample_rate=16000, mels=128, collate=False, **unsupported):
     """extract_features (essentials.py:423-521) over a list of {"audio": path, "transcription"|"sentence"}
-    dicts, with the audio of all of them loaded by one load_batch (one H2D copy, device normalisation).
-    Returns the same per-clip feature dicts as extract_features (for DataCollator)."""
+    dicts, with the audio of all of them loaded by one load_batch (one H2D copy, device normalisation) and
+    the spectrogram and waveform features of all of them computed by one mel.logmel_ragged call, whatever the
+    clip lengths.  Returns the same per-clip feature dicts as extract_features (for DataCollator); their
+    spectrogram and waveform are views of the padded batch tensors.
+
+    collate=True returns what DataCollator(tokenizer)(those dicts) returns (essentials.py:523-574) without its
+    pad and stack copies of the spectrogram and waveform: the padded tensors are the kernel's output as it
+    stands.  Labels, text_ids and pitch go through the collator itself."""
     from . import mel as _mel
 
     if any(unsupported.get(k) for k in ("harmonics", "aperiodics", "pitch_tokens")):
@@ -175,16 +181,26 @@ def extract_features_batch(batches, tokenizer=None, spectrogram=False, waveform=
                 ph = torch.remainder(torch.cumsum(2 * torch.pi * f0 * tframe, dim=-1), 2 * torch.pi)
                 for j, i in enumerate(idx):
                     phase_of[i] = ph[j].to(torch.float32)
+    plan = _mel.ragged_plan(lengths)
+    # a clip with no pool bin (or fewer samples than bins) is extract_features' interpolate branch: the waveform
+    # of such a batch takes the per-clip path
+    pooled_ok = waveform and all(t > 0 and n > t for n, t in zip(plan.n, plan.T))
+    spec_all = pool_all = None
+    if spectrogram or pooled_ok:
+        rm = _mel.logmel_ragged(wave[:, 0], lengths, layout="BMF", pool=pooled_ok)
+        spec_all, pool_all = rm.mel, rm.pool
     out = []
     for i, b in enumerate(batches):
-        n = int(lengths[i])
-        audio = wave[i, 0, :n].contiguous()
+        n = plan.n[i]
         labels = tokenizer.encode(b["transcription" if "transcription" in b else "sentence"]) if tokenizer else []
         s_tensor = w_tensor = None
         if spectrogram:
-            s_tensor = _mel.logmel(audio.unsqueeze(0), layout="BMF")[0]
-        if waveform:
-            target = int((n / sample_rate) * (sample_rate // hop_length))
+            s_tensor = spec_all[i, :, :plan.F[i]]
+        if pooled_ok:
+            w_tensor = pool_all[i:i + 1, :plan.T[i]]
+        elif waveform:
+            audio = wave[i, 0, :n].contiguous()
+            target = plan.T[i]
             if n > target and n == target * hop_length:
                 _, w_tensor = _mel.logmel(audio.unsqueeze(0), layout="BMF", pool=True)
             elif n > target and target > 0:  # as features.extract_features: wave_pool needs 0 < target < n
@@ -194,4 +210,16 @@ def extract_features_batch(batches, tokenizer=None, spectrogram=False, waveform=
                                                            align_corners=False)[0]
         out.append({"waveform": w_tensor, "spectrogram": s_tensor, "pitch_tokens": None, "pitch": pitch_of.get(i),
                     "harmonic": None, "aperiodic": None, "labels": labels, "phase": phase_of.get(i)})
-    return out
+    if not collate:
+        return out
+    from .features import DataCollator
+
+    # the collator's own rule for labels / text_ids / pitch (and a per-clip waveform); the two batch features
+    # are already padded and stacked
+    rest = [dict(f, spectrogram=None, waveform=None if pooled_ok else f["waveform"]) for f in out]
+    batch = DataCollator(tokenizer)(rest)
+    if spectrogram:
+        batch["spectrogram"] = spec_all  # (B, 128, Fmax)
+    if pooled_ok:
+        batch["waveform"] = pool_all.unsqueeze(1)  # (B, 1, Tmax)
+    return batch

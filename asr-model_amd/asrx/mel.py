@@ -11,7 +11,9 @@ torchaudio is not installed here; the restatement is pinned by the known-answer 
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from . import lib, probe
@@ -196,3 +198,106 @@ def wave_pool(wav: torch.Tensor, T: int) -> torch.Tensor:
     out = torch.empty(B, T, device=wav.device, dtype=torch.float32)
     lib.call("asrx_wave_pool", lib.ptr(wav), B, N, wav.stride(0), T, lib.ptr(out), lib.stream())
     return out
+
+
+class RaggedPlan(NamedTuple):
+    """Per-clip extents of a ragged batch (host side of the device clip table of asrx_logmel_ragged)."""
+    n: list      # samples per clip
+    F: list      # mel frames per clip, 1 + n // hop
+    T: list      # waveform pool bins per clip (essentials.py:495)
+    fused: list  # bool: the mel pass's 160-sample block means are the clip's pool (n == hop * T)
+    Fmax: int
+    Tmax: int
+
+    def table(self) -> torch.Tensor:
+        """(B, 4) int32 records {n, F, T, fused}: csrc/logmel.hip MelClip."""
+        return torch.from_numpy(np.stack([np.asarray(self.n, np.int64), np.asarray(self.F, np.int64),
+                                          np.asarray(self.T, np.int64), np.asarray(self.fused, np.int64)],
+                                         1).astype(np.int32))
+
+
+def ragged_plan(lengths, hop: int = HOP, sample_rate: int = SAMPLE_RATE) -> RaggedPlan:
+    """Frame count, pool bin count and "fused pool" flag of every clip of a batch, on the host.
+
+    T is the reference's own expression int((n / sample_rate) * (sample_rate // hop)) in double precision
+    (essentials.py:495), which is not n // hop: n = 4640 gives 28 and n = 9120 gives 56.  A clip is "fused"
+    when its pool bins are exact hop-sized blocks (n == hop * T, T > 0), which the mel tile kernel averages
+    from the samples it already holds; every other clip goes to the general pool, as extract_features
+    sends it to wave_pool."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.is_cuda:
+            raise ValueError("ragged_plan takes host lengths (reading a device tensor would synchronise)")
+        lengths = lengths.tolist()
+    n = np.asarray([int(x) for x in lengths], dtype=np.int64)
+    if n.ndim != 1 or n.size == 0 or bool((n <= 0).any()):
+        raise ValueError("ragged_plan needs a non-empty list of positive clip lengths")
+    F = 1 + n // hop
+    T = ((n / sample_rate) * (sample_rate // hop)).astype(np.int64)  # float64, truncated like int()
+    fused = (T > 0) & (n == T * hop)
+    return RaggedPlan(n.tolist(), F.tolist(), T.tolist(), fused.tolist(), int(F.max()), int(T.max()))
+
+
+class RaggedMel(NamedTuple):
+    mel: torch.Tensor   # (B, Fmax, 128) or (B, 128, Fmax), zero past each clip's F frames
+    pool: object        # (B, Tmax) zero past each clip's T bins, or None
+    F: list
+    T: list
+
+
+def logmel_ragged(wav: torch.Tensor, lengths, layout: str = "BFM", pool: bool = False, out=None, pool_out=None):
+    """Log-mel (and waveform pool) of a batch of clips of different lengths in one pass, written as the
+    collated batch: clip b's result is bit-identical to logmel(wav[b:b+1, :n_b]) (and to the fused pool /
+    wave_pool(wav[b:b+1, :n_b], T_b)) and everything past it is 0, which is what DataCollator's pad and stack
+    of the per-clip features gives (essentials.py:523-574).
+
+    wav: (B, Nmax) float32 device buffer, clip b in wav[b, :lengths[b]]; the rest of a row is ignored.
+    lengths: CPU int64 tensor or sequence (a device tensor raises: reading it would synchronise).
+    pool=True raises ValueError when a clip has T == 0 or n <= T (extract_features interpolates those).
+    -> RaggedMel(mel, pool or None, F per clip, T per clip)."""
+    lib.require_gpu(wav)
+    if wav.dim() != 2 or wav.dtype != torch.float32 or wav.stride(-1) != 1:
+        raise ValueError("logmel_ragged expects (B, Nmax) float32 audio with unit inner stride")
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        raise ValueError("logmel_ragged takes host lengths (reading a device tensor would synchronise)")
+    plan = ragged_plan(lengths)
+    B, Nmax = wav.shape
+    if len(plan.n) != B or max(plan.n) > Nmax:
+        raise ValueError(f"logmel_ragged: {len(plan.n)} lengths (max {max(plan.n)}) for a {tuple(wav.shape)} buffer")
+    if pool and any(t == 0 or n <= t for n, t in zip(plan.n, plan.T)):
+        raise ValueError("logmel_ragged(pool=True): a clip with T == 0 or n <= T takes extract_features' "
+                         "interpolate branch, not the pool")
+    Fmax, Tmax = plan.Fmax, plan.Tmax
+    if layout == "BFM":
+        shape, lay = (B, Fmax, N_MELS), 0
+    elif layout == "BMF":
+        shape, lay = (B, N_MELS, Fmax), 1
+    else:
+        raise ValueError(layout)
+    if out is None:
+        out = torch.empty(shape, device=wav.device, dtype=torch.float32)  # every element is written
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != wav.device:
+        raise ValueError(f"logmel_ragged: out must be a contiguous float32 {shape} tensor on {wav.device}")
+    pooled = None
+    if pool:
+        if pool_out is None:
+            pooled = torch.empty(B, Tmax, device=wav.device, dtype=torch.float32)
+        elif (tuple(pool_out.shape) != (B, Tmax) or pool_out.dtype != torch.float32 or not pool_out.is_contiguous()
+              or pool_out.device != wav.device):
+            raise ValueError(f"logmel_ragged: pool_out must be a contiguous float32 {(B, Tmax)} tensor on {wav.device}")
+        else:
+            pooled = pool_out
+    consts, fbw, fbs = device_consts(wav.device)
+    # the clip table: one non-blocking copy from pinned memory (stream-ordered before the kernels)
+    clips = plan.table().pin_memory().to(wav.device, non_blocking=True)
+    ws = torch.empty(lib.load().asrx_logmel_ws_bytes(B, Nmax) // 4, dtype=torch.float32, device=wav.device)
+    e0 = probe.begin("logmel")
+    lib.call("asrx_logmel_ragged", lib.ptr(wav), B, Nmax, wav.stride(0), lib.ptr(clips), lib.ptr(consts),
+             lib.ptr(fbw), lib.ptr(fbs), lib.ptr(out), lay, Fmax * N_MELS, Fmax, lib.ptr(ws), lib.ptr(pooled),
+             Tmax if pool else 0, lib.stream())
+    # nothing is left for the general pool when the mel pass pooled every clip and no clip has pad bins
+    if pool and not (all(plan.fused) and min(plan.T) == Tmax):
+        lib.call("asrx_wave_pool_ragged", lib.ptr(wav), B, Nmax, wav.stride(0), lib.ptr(clips), lib.ptr(pooled),
+                 Tmax, lib.stream())
+    if e0 is not None:
+        probe.end("logmel", e0, sum(algorithmic_bytes(1, n, pool) for n in plan.n))
+    return RaggedMel(out, pooled, plan.F, plan.T)

@@ -32,6 +32,10 @@
 // waveform pool reads the same LDS samples (16 threads per frame, DPP row sums).
 // Kernel 2 (logmel_floor): the clip-max floor, max(x, clipmax - 8), on the (x + 4) / 4 values; a tile
 // whose minimum is not below the floor is skipped.
+// Ragged batches (asrx_logmel_ragged, asrx_wave_pool_ragged): the RAGGED instantiations of the same
+// kernels read each clip's length, frame count and pool bin count from a device clip table and write
+// the collated, zero-padded batch (what DataCollator builds, essentials.py:523-574) in one pass; per
+// frame and per bin they run the same instructions on the same values as the equal-length entries.
 #include "common.h"
 #include "fft.h"
 
@@ -352,16 +356,29 @@ __device__ __forceinline__ int xcd_block(int bid, int G) {
   return (x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per) + q;
 }
 
+// One record per clip of a ragged batch (asrx/mel.py ragged_plan): n samples, F = 1 + n / 160 frames,
+// T pool bins, fused != 0 when the tile kernel's block means are the clip's pool (n == 160 T).  The
+// kernels clamp n, F and T to the batch extents they were launched with, so no table content can send
+// an access out of bounds.
+struct MelClip {
+  int n, F, T, fused;
+};
+__device__ __forceinline__ int clampi(int v, int64_t hi) { return v < 0 ? 0 : (v > hi ? (int)hi : v); }
+
 // LAYOUT 0 (B, F, 128): every lane stores its two bands straight into the frame's 512-byte row (L2
 // merges the scattered dwords into whole lines), so no staging block is needed and the workgroup's
 // LDS (40.6 KB) lets 4 of them share a CU.  LAYOUT 1 (B, 128, F) stages the tile in LDS for
 // frame-contiguous stores.
-template <int LAYOUT>
+// RAGGED: N, F and T_pool are the batch extents (Nmax, Fmax, Tmax: the strides and the tile grid) and
+// clip b's own n, F, T come from clips[b] (uniform loads).  Samples at or past n are zero for the
+// transform whatever the buffer holds; a tile whose first frame is >= F does no transform, stores zeros
+// and writes the neutral tile statistics; frames in [F, Fmax) of a partly live tile are stored as 0.
+template <int LAYOUT, bool RAGGED>
 __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
     const float* __restrict__ wav, int64_t N, int64_t ld_wav, int vec_ok, int64_t F, int tiles_per_clip,
     int64_t n_tiles, int tiles_per_block, const float* __restrict__ consts, const float* __restrict__ fbw,
     const int* __restrict__ fbs, float* __restrict__ out, int64_t ld_out,
-    float* __restrict__ tstat, float* __restrict__ pool, int64_t T_pool) {
+    float* __restrict__ tstat, float* __restrict__ pool, int64_t T_pool, const MelClip* __restrict__ clips) {
   // (B, F, 128): two sample buffers, the next tile's samples land by LDS-DMA while this tile is
   // transformed; (B, 128, F) keeps one (its staging block takes the room)
   constexpr int NBUF = LAYOUT == 0 ? MEL_NBUF0 : 1;
@@ -410,7 +427,9 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
     const int64_t b = t / tiles_per_clip;
     const int64_t g0 = (t - b * tiles_per_clip) * MEL_FPT * MEL_HOP - MEL_NFFT / 2;
     const float* x = wav + b * ld_wav + g0;
-    if (vec_ok && g0 >= 0 && g0 + MEL_TSAMP <= N) {
+    int64_t n_clip = N;
+    if constexpr (RAGGED) n_clip = clampi(clips[__builtin_amdgcn_readfirstlane((int)b)].n, N);
+    if (vec_ok && g0 >= 0 && g0 + MEL_TSAMP <= n_clip) {
       const float4* x4 = reinterpret_cast<const float4*>(x);
 #pragma unroll
       for (int q = 0; q < MEL_PF; ++q) {
@@ -421,7 +440,7 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
 #pragma unroll 1
       for (int i = tid; i < MEL_TSAMP; i += 256) {
         const int64_t g = g0 + i;
-        dst[i] = (g >= 0 && g < N) ? x[i] : 0.f;
+        dst[i] = (g >= 0 && g < n_clip) ? x[i] : 0.f;
       }
     }
   };
@@ -432,10 +451,19 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
     const int64_t b = t / tiles_per_clip;
     const int64_t f0 = (t - b * tiles_per_clip) * MEL_FPT;
     float* samp = samp_buf[NBUF == 2 ? (int)((t - t_begin) & 1) : 0];
+    int64_t F_clip = F, T_clip = T_pool;  // this clip's frames and pool bins
+    bool fused_clip = true, dead = false;
+    if constexpr (RAGGED) {
+      const MelClip rec = clips[__builtin_amdgcn_readfirstlane((int)b)];
+      F_clip = clampi(rec.F, F);
+      T_clip = clampi(rec.T, T_pool);
+      fused_clip = rec.fused != 0;
+      dead = f0 >= F_clip;  // workgroup-uniform
+    }
     if constexpr (NBUF == 1) {
       __syncthreads();  // the previous tile's readers are done with samp / melst
 #if !(MEL_ABL & 1)
-      stage(t, samp);
+      if (!dead) stage(t, samp);
 #endif
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -448,7 +476,27 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
     // threads per frame, each summing 10 consecutive samples, then a DPP sum inside the 16-lane row
     // (quad_perm xor 1, xor 2, row_half_mirror, row_mirror): no LDS round trips
     static_assert(MEL_HOP == 16 * 10, "the pool splits a hop into 16 runs of 10 samples");
-    if (pool && !(MEL_ABL & 32)) {
+    if constexpr (RAGGED) {
+      if (dead) {  // pad frames of the collated batch: zeros, and statistics no max or floor test sees
+        float* o = out + b * ld_out;
+        const int nf = (int)(F - f0 < MEL_FPT ? (F - f0 < 0 ? 0 : F - f0) : MEL_FPT);
+        if constexpr (LAYOUT == 0) {
+          float4* o4 = reinterpret_cast<float4*>(o + f0 * MEL_BANDS);
+          for (int i = tid; i < nf * MEL_BANDS / 4; i += 256) o4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+          for (int i = tid; i < MEL_FPT * MEL_BANDS; i += 256) {
+            const int m = i / MEL_FPT, fi = i % MEL_FPT;
+            if (fi < nf) o[m * F + f0 + fi] = 0.f;
+          }
+        }
+        if (tid == 0) {
+          tstat[t] = -3.0e38f;
+          tstat[n_tiles + t] = 3.0e38f;
+        }
+        continue;
+      }
+    }
+    if (pool && fused_clip && !(MEL_ABL & 32)) {
 #pragma unroll 1
       for (int i = tid; i < MEL_FPT * 16; i += 256) {
         const int fi = i >> 4, part = i & 15;
@@ -461,7 +509,7 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x141, 0xF, 0xF, false));
         s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x140, 0xF, 0xF, false));
         const int64_t f = f0 + fi;
-        if (part == 0 && f < T_pool) pool[b * T_pool + f] = s * (1.0f / MEL_HOP);
+        if (part == 0 && f < T_clip) pool[b * T_pool + f] = s * (1.0f / MEL_HOP);
       }
     }
 
@@ -634,7 +682,7 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
 #pragma unroll
       for (int q = 0; q < NI; ++q) {
         const int fi = fi0 + q * MEL_WAVES;
-        const bool live = f0 + fi < F;  // wave-uniform
+        const bool live = f0 + fi < F_clip;  // wave-uniform
         // clamp(1e-10).log10(): the clamped value maps to exactly -10 like the correctly rounded
         // library log10; elsewhere log2 * log10(2) is within a few ulp
         const float l_a = acc_a[q] <= 1e-10f ? -10.0f : __builtin_amdgcn_logf(acc_a[q]) * 0.30102999566398120f;
@@ -648,6 +696,13 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
             float* orow = out + b * ld_out + (f0 + fi) * MEL_BANDS;
             orow[band_a] = y_a;
             orow[band_b] = y_b;
+          }
+          if constexpr (RAGGED) {
+            if (!live && f0 + fi < F) {  // pad frame of a partly live tile
+              float* orow = out + b * ld_out + (f0 + fi) * MEL_BANDS;
+              orow[band_a] = 0.f;
+              orow[band_b] = 0.f;
+            }
           }
         } else {
           melst[fi][band_a] = y_a;
@@ -672,9 +727,11 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
       float* o = out + b * ld_out;
       for (int i = tid; i < MEL_FPT * MEL_BANDS / 4; i += 256) {
         const int fi = i / (MEL_BANDS / 4), m4 = (i % (MEL_BANDS / 4)) * 4;
-        if (f0 + fi < F) {
+        if (f0 + fi < F_clip) {
           const float* src = &melst[fi][m4];
           *reinterpret_cast<float4*>(o + (f0 + fi) * MEL_BANDS + m4) = make_float4(src[0], src[1], src[2], src[3]);
+        } else if (RAGGED && f0 + fi < F) {
+          *reinterpret_cast<float4*>(o + (f0 + fi) * MEL_BANDS + m4) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
     }
@@ -682,7 +739,8 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
       float* o = out + b * ld_out;
       for (int i = tid; i < MEL_FPT * MEL_BANDS; i += 256) {
         const int m = i / MEL_FPT, fi = i % MEL_FPT;
-        if (f0 + fi < F) o[m * F + f0 + fi] = melst[fi][m];
+        if (f0 + fi < F_clip) o[m * F + f0 + fi] = melst[fi][m];
+        else if (RAGGED && f0 + fi < F) o[m * F + f0 + fi] = 0.f;
       }
     }
     if (tid == 0) {  // this tile's max and min log value over its live frames (no atomics, no init)
@@ -702,14 +760,25 @@ __global__ __launch_bounds__(256, MEL_WPS) void logmel_tiles_kernel(
 // kernel wrote.  One workgroup per tile: the clip max is the max of the clip's tile maxima; a tile
 // whose minimum is not below the floor is left as it is (every value already final), any other is
 // rewritten as max(y, (f + 4) / 4).
+// RAGGED: F is the batch's Fmax (the (B, 128, F) row stride); the clip max runs over the clip's own live
+// tiles and only its live frames are clamped, so the pad zeros are never compared against the floor.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void logmel_floor_kernel(float* __restrict__ out, int layout, int64_t F,
                                                            int64_t ld_out, int tiles_per_clip, int64_t n_tiles,
-                                                           const float* __restrict__ tstat) {
+                                                           const float* __restrict__ tstat,
+                                                           const MelClip* __restrict__ clips) {
   __shared__ float red[4];
   const int b = blockIdx.y, tl = blockIdx.x, tid = threadIdx.x;
   const float* tm = tstat + (int64_t)b * tiles_per_clip;
+  int64_t F_clip = F;
+  int live_tiles = tiles_per_clip;
+  if constexpr (RAGGED) {
+    F_clip = clampi(clips[b].F, F);
+    live_tiles = (int)((F_clip + MEL_FPT - 1) / MEL_FPT);
+    if (tl >= live_tiles) return;  // a pad tile (workgroup-uniform)
+  }
   float m = -3.0e38f;
-  for (int i = tid; i < tiles_per_clip; i += 256) m = fmaxf(m, tm[i]);
+  for (int i = tid; i < live_tiles; i += 256) m = fmaxf(m, tm[i]);
   m = wave_max(m);
   if ((tid & 63) == 0) red[tid >> 6] = m;
   __syncthreads();
@@ -717,7 +786,7 @@ __global__ __launch_bounds__(256) void logmel_floor_kernel(float* __restrict__ o
   if (!(tstat[n_tiles + (int64_t)b * tiles_per_clip + tl] < floor_v)) return;  // workgroup-uniform
   const float yf = (floor_v + 4.0f) * 0.25f;
   const int64_t f0 = (int64_t)tl * MEL_FPT;
-  const int nf = (int)(F - f0 < MEL_FPT ? F - f0 : MEL_FPT);
+  const int nf = (int)(F_clip - f0 < MEL_FPT ? F_clip - f0 : MEL_FPT);
   float* o = out + b * ld_out;
   if (layout == 0) {  // nf contiguous rows of 128
     float4* o4 = reinterpret_cast<float4*>(o + f0 * MEL_BANDS);
@@ -774,12 +843,53 @@ extern "C" int asrx_logmel(const float* wav, int64_t B, int64_t N, int64_t ld_wa
   const int tiles_per_block = (int)std::max<int64_t>(1, (n_tiles + slots - 1) / slots);
   const int64_t grid = (n_tiles + tiles_per_block - 1) / tiles_per_block;
   const int vec_ok = (ld_wav % 4 == 0) && ((reinterpret_cast<uintptr_t>(wav) & 15) == 0);
-  auto kern = layout == 0 ? logmel_tiles_kernel<0> : logmel_tiles_kernel<1>;
+  auto kern = layout == 0 ? logmel_tiles_kernel<0, false> : logmel_tiles_kernel<1, false>;
   kern<<<(unsigned)grid, 256, 0, stream>>>(wav, N, ld_wav, vec_ok, F, tiles_per_clip, n_tiles, tiles_per_block,
-                                           consts, fbw, fbs, out, ld_out, tstat, pool, T_pool);
-  logmel_floor_kernel<<<dim3((unsigned)tiles_per_clip, (unsigned)B), 256, 0, stream>>>(
-      out, layout, F, ld_out, tiles_per_clip, n_tiles, tstat);
+                                           consts, fbw, fbs, out, ld_out, tstat, pool, T_pool, nullptr);
+  logmel_floor_kernel<false><<<dim3((unsigned)tiles_per_clip, (unsigned)B), 256, 0, stream>>>(
+      out, layout, F, ld_out, tiles_per_clip, n_tiles, tstat, nullptr);
   ASRX_LAUNCHED("asrx_logmel");
+}
+
+// The ragged form of asrx_logmel: the spectrogram branch of extract_features (essentials.py:469-491) for
+// every clip of a batch and DataCollator's pad-and-stack of the results (essentials.py:523-574, pad value
+// 0) in the same two launches.  wav: (B, Nmax) rows at stride ld_wav, clip b occupying [0, n_b); what the
+// buffer holds past n_b is never used.  clips: B device records {n, F = 1 + n / 160, T, fused} (int32 x 4,
+// asrx/mel.py ragged_plan).  out: (B, Fmax, 128) if layout == 0 else (B, 128, Fmax), clip stride ld_out;
+// every element is written: clip b's F_b frames, then exact zeros.  ws: asrx_logmel_ws_bytes(B, Nmax)
+// bytes.  pool: (B, Tmax) or null; clips with fused != 0 (n_b == 160 T_b) get bins [0, T_b) here, the
+// others and the zero bins [T_b, Tmax) come from asrx_wave_pool_ragged.
+extern "C" int asrx_logmel_ragged(const float* wav, int64_t B, int64_t Nmax, int64_t ld_wav, const void* clips,
+                                  const float* consts, const float* fbw, const int* fbs, float* out, int layout,
+                                  int64_t ld_out, int64_t Fmax, void* ws, float* pool, int64_t Tmax,
+                                  hipStream_t stream) {
+  ASRX_REQUIRE(B > 0 && Nmax > 0, "asrx_logmel_ragged: empty input");
+  ASRX_REQUIRE(B < 65536, "asrx_logmel_ragged: too many clips (grid y)");
+  ASRX_REQUIRE(Nmax < (int64_t)1 << 31, "asrx_logmel_ragged: clip lengths are 32-bit (Nmax=%ld)", (long)Nmax);
+  ASRX_REQUIRE(ld_wav >= Nmax, "asrx_logmel_ragged: ld_wav < Nmax");
+  ASRX_REQUIRE(clips && (reinterpret_cast<uintptr_t>(clips) & 15) == 0,
+               "asrx_logmel_ragged: the clip table must be 16-byte aligned");
+  ASRX_REQUIRE(Fmax >= 1 && Fmax <= 1 + Nmax / MEL_HOP,
+               "asrx_logmel_ragged: need 1 <= Fmax <= 1 + Nmax/160 (Fmax=%ld)", (long)Fmax);
+  ASRX_REQUIRE(ld_out >= Fmax * MEL_BANDS, "asrx_logmel_ragged: ld_out too small");
+  ASRX_REQUIRE(layout != 0 || (ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0),
+               "asrx_logmel_ragged: (B, F, 128) layout needs 16-byte aligned rows");
+  ASRX_REQUIRE(!pool || (Tmax > 0 && Tmax <= Nmax / MEL_HOP),
+               "asrx_logmel_ragged: pool needs 0 < Tmax <= Nmax/160 (Tmax=%ld)", (long)Tmax);
+  const int tiles_per_clip = (int)mel_tiles_per_clip(Nmax);
+  const int64_t n_tiles = B * tiles_per_clip;
+  float* tstat = static_cast<float*>(ws);
+  const int64_t slots = 256 * MEL_WPS;  // the same persistent, XCD-grouped walk as asrx_logmel
+  const int tiles_per_block = (int)std::max<int64_t>(1, (n_tiles + slots - 1) / slots);
+  const int64_t grid = (n_tiles + tiles_per_block - 1) / tiles_per_block;
+  const int vec_ok = (ld_wav % 4 == 0) && ((reinterpret_cast<uintptr_t>(wav) & 15) == 0);
+  const MelClip* ct = static_cast<const MelClip*>(clips);
+  auto kern = layout == 0 ? logmel_tiles_kernel<0, true> : logmel_tiles_kernel<1, true>;
+  kern<<<(unsigned)grid, 256, 0, stream>>>(wav, Nmax, ld_wav, vec_ok, Fmax, tiles_per_clip, n_tiles, tiles_per_block,
+                                           consts, fbw, fbs, out, ld_out, tstat, pool, Tmax, ct);
+  logmel_floor_kernel<true><<<dim3((unsigned)tiles_per_clip, (unsigned)B), 256, 0, stream>>>(
+      out, layout, Fmax, ld_out, tiles_per_clip, n_tiles, tstat, ct);
+  ASRX_LAUNCHED("asrx_logmel_ragged");
 }
 
 extern "C" int asrx_mel_frames(int64_t N) { return (int)(1 + N / MEL_HOP); }
@@ -804,6 +914,31 @@ __global__ __launch_bounds__(256) void wave_pool_kernel(const float* __restrict_
     if (lane == 0) out[w] = acc / (float)(e - s);
   }
 }
+// The ragged form: one wave per (clip, bin) of the padded (B, Tmax) output.  Bin i < T_b of a clip that
+// the tile kernel did not pool (fused == 0) is wave_pool_kernel's bin with N = n_b, T = T_b: the same
+// window bounds and the same order of sums.  Bins [T_b, Tmax) of every clip are written as 0.
+__global__ __launch_bounds__(256) void wave_pool_ragged_kernel(const float* __restrict__ wav, int64_t Nmax,
+                                                               int64_t ld_wav, const MelClip* __restrict__ clips,
+                                                               int64_t Tmax, int64_t B, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nw = (int64_t)gridDim.x * 4;
+  for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < B * Tmax; w += nw) {
+    const int64_t b = w / Tmax, i = w % Tmax;
+    const MelClip rec = clips[b];
+    const int64_t N = clampi(rec.n, Nmax), T = clampi(rec.T, Tmax);
+    if (i >= T) {
+      if (lane == 0) out[w] = 0.f;
+      continue;
+    }
+    if (rec.fused != 0) continue;
+    const int64_t s = (i * N) / T, e = ((i + 1) * N + T - 1) / T;
+    const float* x = wav + b * ld_wav;
+    float acc = 0.f;
+    for (int64_t j = s + lane; j < e; j += 64) acc += x[j];
+    acc = wave_sum(acc);
+    if (lane == 0) out[w] = acc / (float)(e - s);
+  }
+}
 }  // namespace asrx
 
 extern "C" int asrx_wave_pool(const float* wav, int64_t B, int64_t N, int64_t ld_wav, int64_t T, float* out,
@@ -813,4 +948,25 @@ extern "C" int asrx_wave_pool(const float* wav, int64_t B, int64_t N, int64_t ld
   const unsigned grid = (unsigned)std::min<int64_t>((waves + 3) / 4, 65536);
   asrx::wave_pool_kernel<<<grid, 256, 0, stream>>>(wav, N, ld_wav, T, B, out);
   ASRX_LAUNCHED("asrx_wave_pool");
+}
+
+// The ragged form of asrx_wave_pool: the waveform branch of extract_features (essentials.py:493-510) for
+// every clip of a batch whose pool the mel pass did not fuse, and DataCollator's zero padding of all of
+// them to Tmax bins (essentials.py:523-574).  wav (B, Nmax) at row stride ld_wav, clips as for
+// asrx_logmel_ragged, out (B, Tmax); bins [0, T_b) of the clips with fused != 0 are left to
+// asrx_logmel_ragged.
+extern "C" int asrx_wave_pool_ragged(const float* wav, int64_t B, int64_t Nmax, int64_t ld_wav, const void* clips,
+                                     float* out, int64_t Tmax, hipStream_t stream) {
+  ASRX_REQUIRE(B > 0 && Nmax > 0 && Tmax > 0 && Tmax <= Nmax,
+               "asrx_wave_pool_ragged: need 0 < Tmax <= Nmax (Nmax=%ld Tmax=%ld)", (long)Nmax, (long)Tmax);
+  ASRX_REQUIRE(B < 65536, "asrx_wave_pool_ragged: too many clips");
+  ASRX_REQUIRE(Nmax < (int64_t)1 << 31, "asrx_wave_pool_ragged: clip lengths are 32-bit (Nmax=%ld)", (long)Nmax);
+  ASRX_REQUIRE(ld_wav >= Nmax, "asrx_wave_pool_ragged: ld_wav < Nmax");
+  ASRX_REQUIRE(clips && (reinterpret_cast<uintptr_t>(clips) & 15) == 0,
+               "asrx_wave_pool_ragged: the clip table must be 16-byte aligned");
+  const int64_t waves = B * Tmax;
+  const unsigned grid = (unsigned)std::min<int64_t>((waves + 3) / 4, 65536);
+  asrx::wave_pool_ragged_kernel<<<grid, 256, 0, stream>>>(wav, Nmax, ld_wav, static_cast<const asrx::MelClip*>(clips),
+                                                          Tmax, B, out);
+  ASRX_LAUNCHED("asrx_wave_pool_ragged");
 }

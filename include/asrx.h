@@ -62,6 +62,21 @@ int asrx_logmel(const float* wav, int64_t B, int64_t N, int64_t ld_wav, const fl
  * mean of samples [floor(i N / T), ceil((i + 1) N / T)); wav (B, N) at row stride ld_wav, out (B, T). */
 int asrx_wave_pool(const float* wav, int64_t B, int64_t N, int64_t ld_wav, int64_t T, float* out,
                    asrx_stream_t stream);
+/* Ragged batch: the same features for B clips of different lengths, written as the collated, zero-padded
+ * batch DataCollator stacks (essentials.py:523-574, pad value 0).  wav (B,Nmax) at row stride ld_wav, clip b
+ * in [0, n_b) (what lies past n_b is never used); clips = B device records of four int32 {n, F = 1 + n/160,
+ * T pool bins, fused} (asrx/mel.py ragged_plan), 16-byte aligned; out (B,Fmax,128) when layout==0 or
+ * (B,128,Fmax) when layout==1, clip stride ld_out, every element written (F_b frames, then zeros); ws of
+ * asrx_logmel_ws_bytes(B, Nmax) bytes; pool (B,Tmax) or NULL: clips with fused != 0 (n_b == 160*T_b) get
+ * bins [0, T_b).  Replaces essentials.py:469-491 per clip and the collator's pad + stack. */
+int asrx_logmel_ragged(const float* wav, int64_t B, int64_t Nmax, int64_t ld_wav, const void* clips,
+                       const float* consts, const float* fbw, const int* fbs, float* out, int layout,
+                       int64_t ld_out, int64_t Fmax, void* ws, float* pool, int64_t Tmax,
+                       asrx_stream_t stream);
+/* adaptive_avg_pool1d(audio_b, T_b) (essentials.py:493-510) for the clips with fused == 0, and zeros in bins
+ * [T_b, Tmax) of every clip; out (B,Tmax).  Bins [0, T_b) of the fused clips belong to asrx_logmel_ragged. */
+int asrx_wave_pool_ragged(const float* wav, int64_t B, int64_t Nmax, int64_t ld_wav, const void* clips,
+                          float* out, int64_t Tmax, asrx_stream_t stream);
 
 /* ---- audio IO: load_wave's soundfile.read + peak normalisation,
  *      essentials.py:301-319, for the prepare_datasets path (998-1026). -------------------------
