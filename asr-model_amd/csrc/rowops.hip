@@ -1428,7 +1428,7 @@ __global__ void lincomb_kernel(const float* __restrict__ x, const float* __restr
   }
 }
 
-// float4 forms of lincomb / act_fwd / act_bwd (n % 4 == 0, 16-byte aligned, n / 4 < 2^32): two float4 per
+// float4 forms of lincomb / act_fwd / act_bwd (n % 4 == 0, 16-byte aligned, n / 4 < 2^31): two float4 per
 // thread and iteration, every load issued before any use, 32-bit indices.  The scalar forms moved one float
 // per thread per iteration behind a vmcnt(0) each (~3.9 TB/s); the per-element arithmetic is unchanged,
 // so the results are bit-identical.
@@ -1474,6 +1474,7 @@ __device__ __forceinline__ float act_deriv(int act, float v) {
       const float s = sigmoid_f(v);
       return s * (1.f - s);
     }
+    case ACT_RELU: return v > 0.f ? 1.f : 0.f;
     default: return 1.f;
   }
 }
@@ -1511,6 +1512,7 @@ __global__ void act_bwd_kernel(const float* __restrict__ g, const float* __restr
         d = s * (1.f - s);
         break;
       }
+      case ACT_RELU: d = v > 0.f ? 1.f : 0.f; break;
       default: d = 1.f;
     }
     dx[i] = g[i] * d;
@@ -1606,6 +1608,7 @@ __device__ __forceinline__ float act_grad(int act, float v) {
       const float s = sigmoid_f(v);
       return s * (1.f - s);
     }
+    case ACT_RELU: return v > 0.f ? 1.f : 0.f;
     default: return 1.f;
   }
 }
@@ -2522,6 +2525,9 @@ int asrx_layernorm_bwd(const float* dy, const float* x, const float* w, const fl
 template <typename TX>
 static int small_linear_fwd_t(const TX* x, const float* W, const float* b, float* y, int64_t rows, int64_t K,
                               int64_t N, int act, hipStream_t stream) {
+  // the backward differentiates the sigmoid only (and the caller the row softmax): no other activation here
+  ASRX_REQUIRE(act == ACT_NONE || act == ACT_SIGMOID || act == ACT_SOFTMAX,
+               "small_linear: act %d unsupported (none, sigmoid or the row softmax)", act);
   switch (N) {
     case 1: LAUNCH_ROWS((small_linear_fwd_kernel<1, TX>), rows, 0, x, W, b, y, rows, (int)K, act); break;
     case 2: LAUNCH_ROWS((small_linear_fwd_kernel<2, TX>), rows, 0, x, W, b, y, rows, (int)K, act); break;
@@ -2586,6 +2592,7 @@ static int sl_workspace(hipStream_t stream, float** ws) {
 template <typename TX>
 static int small_linear_bwd_t(const float* dy, const float* y, const TX* x, const float* W, float* dx, float* dW,
                               float* db, int64_t rows, int64_t K, int64_t N, int act, float beta, hipStream_t stream) {
+  ASRX_REQUIRE(act == ACT_NONE || act == ACT_SIGMOID, "small_linear_bwd: act %d unsupported (none or sigmoid)", act);
   const size_t shm = (size_t)RW * (N * K + N) * sizeof(float);
   ASRX_REQUIRE(shm <= 64 * 1024, "small_linear_bwd: K too large");
   const unsigned g = row_grid(rows, 1024);

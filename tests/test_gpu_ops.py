@@ -550,7 +550,8 @@ def test_attention_fp8_mode_forward_only(cuda):
 
 
 @pytest.mark.parametrize("B,T,C,sid_base,act,act2", [(2, 101, 384, 0, "gelu", "none"), (3, 77, 64, 64, "gelu", "none"),
-                                                     (1, 33, 8, 5, "none", "none"), (2, 50, 384, 3, "gelu", "gelu")])
+                                                     (1, 33, 8, 5, "none", "none"), (2, 50, 384, 3, "gelu", "gelu"),
+                                                     (2, 50, 384, 3, "relu", "gelu"), (2, 50, 384, 3, "gelu", "relu")])
 def test_act_dropout_fused(cuda, B, T, C, sid_base, act, act2):
     """Fused act + dropout (encoder layer tail) and the float4 dropout: masks equal the oracle's keyed
     mask (keep iff uniform(key, (sid*C + c)*8192 + t) >= p, oracle/keys.py), forward/backward
