@@ -137,8 +137,16 @@ __device__ __forceinline__ void store(const Stage<NJ, ABF>& st, char* At, char* 
 #define P2_DEPTH 3  // register stages in flight (k-steps of prefetch)
 #endif
 
-template <int NJ, bool ABF, int ACT, bool RES, bool ROT = false>
+// The (NJ, ABF, EPI) combinations of gemm_p2_kernel the entry points use (each with every activation for
+// Epi::Plain, without one otherwise), instantiated in the gemm_p2_*.hip units; any other fails to compile.
+constexpr bool p2_built(int nj, bool abf, Epi e) {
+  return e == Epi::Plain ? nj == 2 || nj == 3 : e == Epi::Res ? nj == 3 && !abf : e == Epi::Rot && nj == 3;
+}
+
+template <int NJ, bool ABF, int ACT, Epi EPI>
 __global__ __launch_bounds__(p2::NT2, 2) void gemm_p2_kernel(Params p, int ntiles) {
+  static_assert(p2_built(NJ, ABF, EPI), "not a gemm_p2_kernel instantiation (p2_built)");
+  static_assert(EPI == Epi::Plain || ACT == ACT_NONE, "the residual and rotary epilogues take no activation");
   using namespace p2;
   typedef Geo<NJ, ABF> GE;
   constexpr int BN = GE::BN, NT = 2 * NJ;
@@ -257,7 +265,7 @@ __global__ __launch_bounds__(p2::NT2, 2) void gemm_p2_kernel(Params p, int ntile
 #endif
     if (ce.kk == nk - 1) {
 #if !(P2_ABL & 8)
-      epilogue_lds<NJ, ACT, RES, ROT>(p, acc, bias_s[ce.j & 1], ce.m0, ce.n0, wm, wn, lr, lk, ep);
+      epilogue_lds<NJ, ACT, EPI>(p, acc, bias_s[ce.j & 1], ce.m0, ce.n0, wm, wn, lr, lk, ep);
 #else
       {  // the accumulators feed a never-taken store
         float t = 0.f;
@@ -285,10 +293,10 @@ __global__ __launch_bounds__(p2::NT2, 2) void gemm_p2_kernel(Params p, int ntile
 }
 
 // launch: resident workgroups (2 per CU) walk the tiles persistently
-template <int NJ, bool ABF, int ACT, bool RES, bool ROT = false>
+template <int NJ, bool ABF, int ACT, Epi EPI>
 void launch_p2(const Params& p, hipStream_t s) {
   static int resident = 0;
-  const void* fn = (const void*)gemm_p2_kernel<NJ, ABF, ACT, RES, ROT>;
+  const void* fn = (const void*)gemm_p2_kernel<NJ, ABF, ACT, EPI>;
   if (!resident) {
     int per_cu = 0, dev = 0, cus = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, p2::NT2, 0);
@@ -298,21 +306,21 @@ void launch_p2(const Params& p, hipStream_t s) {
   }
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + p2::Geo<NJ, ABF>::BN - 1) / p2::Geo<NJ, ABF>::BN);
   const int grid = std::min(tiles, resident);
-  gemm_p2_kernel<NJ, ABF, ACT, RES, ROT><<<grid, p2::NT2, 0, s>>>(p, tiles);
+  gemm_p2_kernel<NJ, ABF, ACT, EPI><<<grid, p2::NT2, 0, s>>>(p, tiles);
 }
 
-// dispatch over the activation (runtime act -> template)
-template <int NJ, bool ABF, bool RES>
+// dispatch over the activation (runtime act -> template); the residual and rotary epilogues have none
+template <int NJ, bool ABF, Epi EPI>
 void launch_p2_act(const Params& p, hipStream_t s) {
-  if constexpr (RES) {
-    launch_p2<NJ, ABF, ACT_NONE, true>(p, s);
+  if constexpr (EPI != Epi::Plain) {
+    launch_p2<NJ, ABF, ACT_NONE, EPI>(p, s);
   } else {
     switch (p.act) {
-      case ACT_GELU: launch_p2<NJ, ABF, ACT_GELU, false>(p, s); break;
-      case ACT_SILU: launch_p2<NJ, ABF, ACT_SILU, false>(p, s); break;
-      case ACT_SIGMOID: launch_p2<NJ, ABF, ACT_SIGMOID, false>(p, s); break;
-      case ACT_RELU: launch_p2<NJ, ABF, ACT_RELU, false>(p, s); break;
-      default: launch_p2<NJ, ABF, ACT_NONE, false>(p, s); break;
+      case ACT_GELU: launch_p2<NJ, ABF, ACT_GELU, EPI>(p, s); break;
+      case ACT_SILU: launch_p2<NJ, ABF, ACT_SILU, EPI>(p, s); break;
+      case ACT_SIGMOID: launch_p2<NJ, ABF, ACT_SIGMOID, EPI>(p, s); break;
+      case ACT_RELU: launch_p2<NJ, ABF, ACT_RELU, EPI>(p, s); break;
+      default: launch_p2<NJ, ABF, ACT_NONE, EPI>(p, s); break;
     }
   }
 }
@@ -320,22 +328,21 @@ void launch_p2_act(const Params& p, hipStream_t s) {
 }  // namespace wn
 }  // namespace asrx
 
-#ifndef ASRX_P2_INSTANTIATE
-#define ASRX_P2_DECL(NJ, ABF, RES) extern template void asrx::wn::launch_p2_act<NJ, ABF, RES>(const asrx::wn::Params&, hipStream_t);
+// As gemm_wr.h: a gemm_p2_*.hip unit defines ASRX_P2_INSTANTIATE and lists its instances; other units declare.
+#ifdef ASRX_P2_INSTANTIATE
+#define ASRX_P2_EXTERN
 #else
-#define ASRX_P2_DECL(NJ, ABF, RES) template void asrx::wn::launch_p2_act<NJ, ABF, RES>(const asrx::wn::Params&, hipStream_t);
+#define ASRX_P2_EXTERN extern
 #endif
+#define ASRX_P2_INST(NJ, ABF, EPI)                                                               \
+  ASRX_P2_EXTERN template void asrx::wn::launch_p2_act<NJ, asrx::wn::ABF, asrx::wn::Epi::EPI>( \
+      const asrx::wn::Params&, hipStream_t);
 #ifndef ASRX_P2_INSTANTIATE
-#define ASRX_P2_DECL_ROT(NJ, ABF) extern template void asrx::wn::launch_p2<NJ, ABF, asrx::ACT_NONE, false, true>(const asrx::wn::Params&, hipStream_t);
-#else
-#define ASRX_P2_DECL_ROT(NJ, ABF) template void asrx::wn::launch_p2<NJ, ABF, asrx::ACT_NONE, false, true>(const asrx::wn::Params&, hipStream_t);
-#endif
-#ifndef ASRX_P2_INSTANTIATE
-ASRX_P2_DECL_ROT(3, true)
-ASRX_P2_DECL_ROT(3, false)
-ASRX_P2_DECL(3, false, false)
-ASRX_P2_DECL(3, true, false)
-ASRX_P2_DECL(2, false, false)
-ASRX_P2_DECL(2, true, false)
-ASRX_P2_DECL(3, false, true)
+ASRX_P2_INST(3, BF16A, Rot)
+ASRX_P2_INST(3, F32A, Rot)
+ASRX_P2_INST(3, F32A, Plain)
+ASRX_P2_INST(3, BF16A, Plain)
+ASRX_P2_INST(2, F32A, Plain)
+ASRX_P2_INST(2, BF16A, Plain)
+ASRX_P2_INST(3, F32A, Res)
 #endif

@@ -3,5 +3,5 @@
 #define ASRX_P2_INSTANTIATE
 #include "gemm_p2.h"
 
-ASRX_P2_DECL(2, false, false)
-ASRX_P2_DECL(2, true, false)
+ASRX_P2_INST(2, F32A, Plain)
+ASRX_P2_INST(2, BF16A, Plain)

@@ -3,4 +3,4 @@
 #define ASRX_P2_INSTANTIATE
 #include "gemm_p2.h"
 
-ASRX_P2_DECL(3, false, true)
+ASRX_P2_INST(3, F32A, Res)

@@ -3,5 +3,5 @@
 #define ASRX_P2_INSTANTIATE
 #include "gemm_p2.h"
 
-ASRX_P2_DECL_ROT(3, true)
-ASRX_P2_DECL_ROT(3, false)
+ASRX_P2_INST(3, BF16A, Rot)
+ASRX_P2_INST(3, F32A, Rot)

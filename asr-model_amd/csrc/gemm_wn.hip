@@ -13,23 +13,30 @@
 // + 16: the AbbyNormal router at d = 64 on gemm_wr_kernel instead of router64_kernel (A/B, tests).
 // Default 5.
 static int g_wide_variant = 5;
-static bool ws_on() { return (g_wide_variant & 4) != 0; }
-static bool ws_any() { return (g_wide_variant & 8) != 0; }  // + 8: every shape gemm_ws can run (tests)
 extern "C" int asrx_set_gemm_variant(int v) {
   const int old = g_wide_variant;
   g_wide_variant = v;
   return old;
 }
-// gemm_p2_kernel takes: no k3 conv, float4-aligned C / Z (LDS-staged epilogue), tile widths 3 and 2
-// (measured, profiles/r05_p2_micro.txt: bf16-stored A 5-10 % faster at every shape; fp32 A faster up to 96000
-// rows but 9-18 % slower at 192064 rows, where its four A loads per thread and k-step cost more than the
-// overlap gains -- so fp32 A at >= 131072 rows stays on gemm_wr_kernel)
-static bool p2_ok(const asrx::wn::Params& p, int conv, int nj, int a_bf16) {
-  if (!a_bf16 && p.M >= 131072) return false;
+
+// The kernel of a plain, residual or rotary product (asrx_gemm_wn_ex, _res, _rot): gemm_ws where it is on and
+// takes the launch, else gemm_p2 where it does, else gemm_wr.  Every choice computes the same bits, so only a
+// profile shows a change here.
+enum class WideKernel { WS, P2, WR };
+static WideKernel wide_kernel(const asrx::wn::Params& p, asrx::wn::Epi epi, int conv, int nj, int a_bf16) {
+  const int v = g_wide_variant;
+  // + 4: gemm_ws on; + 8: at every shape it can run (tests), not only those where it measured faster (ws_ok)
+  if ((v & 4) != 0 && !conv && asrx::wn::ws_ok(p, a_bf16, (v & 8) != 0)) return WideKernel::WS;
+  // gemm_p2_kernel takes: no k3 conv, float4-aligned C / Z (LDS-staged epilogue), tile widths 3 and 2 -- for the
+  // residual and rotary epilogues 3 only, the one width they are instantiated at
+  // (measured, profiles/r05_p2_micro.txt: bf16-stored A 5-10 % faster at every shape; fp32 A faster up to 96000
+  // rows but 9-18 % slower at 192064 rows, where its four A loads per thread and k-step cost more than the
+  // overlap gains -- so fp32 A at >= 131072 rows stays on gemm_wr_kernel)
   const bool vec = ((p.N | p.ldc) & 3) == 0 && ((uintptr_t)p.C & 15) == 0 && ((uintptr_t)p.Z & 15) == 0 &&
                    ((uintptr_t)p.Cb & 7) == 0;
-  return (g_wide_variant & 3) >= 1 && !conv && (nj == 3 || nj == 2 || (nj == 1 && (g_wide_variant & 3) == 2)) &&
-         vec && p.K >= 64;
+  const bool width = epi == asrx::wn::Epi::Plain ? nj == 3 || nj == 2 || (nj == 1 && (v & 3) == 2) : nj == 3;
+  if ((a_bf16 || p.M < 131072) && (v & 3) >= 1 && !conv && width && vec && p.K >= 64) return WideKernel::P2;
+  return WideKernel::WR;
 }
 
 namespace asrx {
@@ -115,6 +122,84 @@ extern "C" int asrx_weights_to_bf16(const void* tab, int64_t n, int64_t max_elem
   ASRX_LAUNCHED("asrx_weights_to_bf16");
 }
 
+// What the wide-GEMM entry points below share.
+//
+// wide_check: the four checks each of them makes, in this order -- a non-empty problem, A and W 16-byte aligned,
+// K and the row strides divisible, operands that span < 2^31 elements.  An entry point extends the second and
+// third with conditions of its own (Also: their value, and its wording of the whole check) and may name a failure
+// of its own that is reported right after the first check (early) or right before the last (late).  0, or 2 with
+// the message set.
+struct Also { bool ok; const char* msg; };
+static int wide_check(const char* name, const void* A, int a_bf16, int64_t lda, const void* W, int64_t ldw, int64_t M,
+                      int64_t N, int64_t K, Also aligned = {true, "A/W must be 16-byte aligned"},
+                      Also strides = {true, "K%8, lda%4, ldw%8 required"}, const char* early = nullptr,
+                      const char* late = nullptr) {
+  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "%s: empty problem", name);
+  ASRX_REQUIRE(!early, "%s: %s", name, early);
+  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && aligned.ok, "%s: %s", name, aligned.msg);
+  ASRX_REQUIRE(K % 8 == 0 && lda % (a_bf16 ? 8 : 4) == 0 && ldw % 8 == 0 && strides.ok, "%s: %s", name, strides.msg);
+  ASRX_REQUIRE(!late, "%s: %s", name, late);
+  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "%s: operand spans >= 2^31 elements", name);
+  return 0;
+}
+
+// wide_params: the operands every product has; every other field is null / 0 (convF = convC = 1: no conv) and is
+// assigned by name where an entry point uses it.
+static wn::Params wide_params(const void* A, int64_t lda, const unsigned short* W, int64_t ldw, float* C, int64_t ldc,
+                              const float* bias, float* Z, int64_t M, int64_t N, int64_t K, float alpha = 1.f,
+                              float beta = 0.f, int act = ACT_NONE) {
+  wn::Params p{};
+  p.A = (const float*)A; p.lda = (int)lda; p.W = W; p.ldw = (int)ldw;
+  p.C = C; p.ldc = (int)ldc; p.bias = bias; p.Z = Z;
+  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.convF = p.convC = 1;
+  p.alpha = alpha; p.beta = beta; p.act = act;
+  return p;
+}
+
+// run_wr / run_wide: runtime tile width (3, 2, otherwise 1), conv and A storage -> the template instance.  Only
+// instances that exist are named (wr_built / p2_built / ws_built beside the lists in gemm_wr.h, gemm_p2.h,
+// gemm_ws.h): naming another would compile a second copy of the kernel into this unit.  false: no instance
+// (launched() reports it; the entry points' own checks leave no such call).
+template <wn::Epi EPI, int NJ, bool CONV, bool ABF>
+static bool wr_instance(const wn::Params& p, hipStream_t s) {
+  if constexpr (wn::wr_built(NJ, CONV, ABF, EPI)) wn::launch_wr<NJ, CONV, ABF, EPI>(p, s);
+  return wn::wr_built(NJ, CONV, ABF, EPI);
+}
+template <wn::Epi EPI, int NJ, bool ABF>
+static bool p2_instance(const wn::Params& p, hipStream_t s) {
+  if constexpr (wn::p2_built(NJ, ABF, EPI)) wn::launch_p2_act<NJ, ABF, EPI>(p, s);
+  return wn::p2_built(NJ, ABF, EPI);
+}
+template <wn::Epi EPI, bool ABF>
+static bool ws_instance(const wn::Params& p, hipStream_t s) {
+  if constexpr (wn::ws_built(ABF, EPI)) wn::launch_ws_act<ABF, EPI>(p, s);
+  return wn::ws_built(ABF, EPI);
+}
+template <wn::Epi EPI, int NJ>
+static bool run_wr_nj(const wn::Params& p, int conv, int a_bf16, hipStream_t s) {
+  if (conv) return a_bf16 ? wr_instance<EPI, NJ, wn::CONV3, wn::BF16A>(p, s) : wr_instance<EPI, NJ, wn::CONV3, wn::F32A>(p, s);
+  return a_bf16 ? wr_instance<EPI, NJ, wn::ROWS, wn::BF16A>(p, s) : wr_instance<EPI, NJ, wn::ROWS, wn::F32A>(p, s);
+}
+template <wn::Epi EPI>  // gemm_wr_kernel only
+static bool run_wr(const wn::Params& p, int conv, int nj, int a_bf16, hipStream_t s) {
+  return nj == 3 ? run_wr_nj<EPI, 3>(p, conv, a_bf16, s)
+                 : nj == 2 ? run_wr_nj<EPI, 2>(p, conv, a_bf16, s) : run_wr_nj<EPI, 1>(p, conv, a_bf16, s);
+}
+template <wn::Epi EPI>  // the kernel wide_kernel chooses; gemm_p2 runs widths 2 and 1 on its 128 x 128 (NJ = 2) tile
+static bool run_wide(const wn::Params& p, int conv, int nj, int a_bf16, hipStream_t s) {
+  switch (wide_kernel(p, EPI, conv, nj, a_bf16)) {
+    case WideKernel::WS: return a_bf16 ? ws_instance<EPI, wn::BF16A>(p, s) : ws_instance<EPI, wn::F32A>(p, s);
+    case WideKernel::P2:
+      if (nj == 3) return a_bf16 ? p2_instance<EPI, 3, wn::BF16A>(p, s) : p2_instance<EPI, 3, wn::F32A>(p, s);
+      return a_bf16 ? p2_instance<EPI, 2, wn::BF16A>(p, s) : p2_instance<EPI, 2, wn::F32A>(p, s);
+    default: return run_wr<EPI>(p, conv, nj, a_bf16, s);
+  }
+}
+static int launched(bool ran, const char* name) {
+  ASRX_REQUIRE(ran, "%s: no kernel instance for this call", name);
+  return check_launch(name);
+}
+
 // Y (M x N, ldc) = act(alpha * A W^T + beta * Y + bias); A fp32 (M x K, lda) or its k3 im2col
 // (conv: lda = channels, K = 3 * channels, segment length convF); W bf16 (N x K, ldw).  nj selects
 // the tile width 128 * nj (1..3).
@@ -122,17 +207,12 @@ extern "C" int asrx_gemm_wn(const float* A, int64_t lda, int conv, int64_t convF
                             const unsigned short* W, int64_t ldw, float* C, int64_t ldc, const float* bias, float* Z,
                             int64_t M, int64_t N, int64_t K, float alpha, float beta, int act, int nj,
                             hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0, "asrx_gemm_wn: A/W must be 16-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % 4 == 0 && ldw % 8 == 0, "asrx_gemm_wn: K%%8, lda%%4, ldw%%8 required");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn", A, 0, lda, W, ldw, M, N, K)) return rc;
   ASRX_REQUIRE(!conv || (convF > 0 && convC % 4 == 0), "asrx_gemm_wn: conv needs F > 0 and C %% 4 == 0");
-  wn::Params p{A, (int)lda, W, (int)ldw, C, (int)ldc, bias, Z, (int)M, (int)N, (int)K,
-               (int)(convF > 0 ? convF : 1), (int)(convC > 0 ? convC : 1), alpha, beta, act, nullptr, nullptr};
-  if (nj == 3) conv ? wn::launch_wr<3, true>(p, stream) : wn::launch_wr<3, false>(p, stream);
-  else if (nj == 2) conv ? wn::launch_wr<2, true>(p, stream) : wn::launch_wr<2, false>(p, stream);
-  else conv ? wn::launch_wr<1, true>(p, stream) : wn::launch_wr<1, false>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn");
+  wn::Params p = wide_params(A, lda, W, ldw, C, ldc, bias, Z, M, N, K, alpha, beta, act);
+  p.convF = (int)(convF > 0 ? convF : 1);
+  p.convC = (int)(convC > 0 ? convC : 1);
+  return launched(run_wr<wn::Epi::Plain>(p, conv, nj, 0, stream), "asrx_gemm_wn");
 }
 
 // asrx_gemm_wn with storage types: A fp32 (a_bf16 = 0) or bf16 (1); C fp32 (c_bf16 = 0) or bf16 (1,
@@ -142,30 +222,19 @@ extern "C" int asrx_gemm_wn_ex(const void* A, int a_bf16, int64_t lda, int conv,
                                const unsigned short* W, int64_t ldw, void* C, int c_bf16, int64_t ldc,
                                const float* bias, float* Z, int64_t M, int64_t N, int64_t K, float alpha, float beta,
                                int act, int nj, const int* mtiles, const int* n_mtiles, hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_ex: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0, "asrx_gemm_wn_ex: A/W must be 16-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % (a_bf16 ? 8 : 4) == 0 && ldw % 8 == 0,
-               "asrx_gemm_wn_ex: K%%8, lda%%4 (fp32) / lda%%8 (bf16), ldw%%8 required");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_ex: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn_ex", A, a_bf16, lda, W, ldw, M, N, K, {true, "A/W must be 16-byte aligned"},
+                          {true, "K%8, lda%4 (fp32) / lda%8 (bf16), ldw%8 required"}))
+    return rc;
   ASRX_REQUIRE(!conv || (convF > 0 && convC % (a_bf16 ? 8 : 4) == 0), "asrx_gemm_wn_ex: conv needs F > 0 and C %% 4 (8 for bf16)");
   ASRX_REQUIRE(!c_bf16 || beta == 0.f, "asrx_gemm_wn_ex: a bf16 output takes beta = 0");
   ASRX_REQUIRE(!(conv && mtiles), "asrx_gemm_wn_ex: tile lists are for plain GEMMs");
-  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, c_bf16 ? nullptr : (float*)C, (int)ldc, bias, Z, (int)M,
-               (int)N, (int)K, (int)(convF > 0 ? convF : 1), (int)(convC > 0 ? convC : 1), alpha, beta, act,
-               nullptr, nullptr, mtiles, n_mtiles, c_bf16 ? (unsigned short*)C : nullptr};
-#define ASRX_WN_EX(NJV)                                                                              \
-  if (a_bf16) conv ? wn::launch_wr<NJV, true, false, true>(p, stream) : wn::launch_wr<NJV, false, false, true>(p, stream); \
-  else conv ? wn::launch_wr<NJV, true>(p, stream) : wn::launch_wr<NJV, false>(p, stream);
-  if (ws_on() && !conv && wn::ws_ok(p, a_bf16, ws_any())) {
-    a_bf16 ? wn::launch_ws_act<true>(p, stream) : wn::launch_ws_act<false>(p, stream);
-  } else if (p2_ok(p, conv, nj, a_bf16)) {
-    if (nj == 3) a_bf16 ? wn::launch_p2_act<3, true, false>(p, stream) : wn::launch_p2_act<3, false, false>(p, stream);
-    else a_bf16 ? wn::launch_p2_act<2, true, false>(p, stream) : wn::launch_p2_act<2, false, false>(p, stream);  // nj 2 / 1
-  } else if (nj == 3) { ASRX_WN_EX(3) }
-  else if (nj == 2) { ASRX_WN_EX(2) }
-  else { ASRX_WN_EX(1) }
-#undef ASRX_WN_EX
-  ASRX_LAUNCHED("asrx_gemm_wn_ex");
+  wn::Params p = wide_params(A, lda, W, ldw, c_bf16 ? nullptr : (float*)C, ldc, bias, Z, M, N, K, alpha, beta, act);
+  p.convF = (int)(convF > 0 ? convF : 1);
+  p.convC = (int)(convC > 0 ? convC : 1);
+  p.mtiles = mtiles;
+  p.n_mtiles = n_mtiles;
+  p.Cb = c_bf16 ? (unsigned short*)C : nullptr;
+  return launched(run_wide<wn::Epi::Plain>(p, conv, nj, a_bf16, stream), "asrx_gemm_wn_ex");
 }
 
 // Tied logits with the cross entropy's statistics fused (model.py:629 logits = x @ token.weight^T,
@@ -175,41 +244,31 @@ extern "C" int asrx_gemm_wn_ex(const void* A, int a_bf16, int64_t lda, int conv,
 // the logits.
 extern "C" int asrx_gemm_wn_ce(const void* A, int64_t lda, const unsigned short* W, int64_t ldw, unsigned short* Zb,
                                int64_t ldc, float* part, int64_t M, int64_t N, int64_t K, int nj, hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_ce: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)Zb & 7) == 0 &&
-                   ((uintptr_t)part & 7) == 0,
-               "asrx_gemm_wn_ce: A/W 16-byte, Zb/part 8-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && N % 4 == 0 && ldc % 4 == 0,
-               "asrx_gemm_wn_ce: K, lda, ldw %% 8 and N, ldc %% 4 required");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_ce: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn_ce", A, 1, lda, W, ldw, M, N, K,
+                          {((uintptr_t)Zb & 7) == 0 && ((uintptr_t)part & 7) == 0, "A/W 16-byte, Zb/part 8-byte aligned"},
+                          {N % 4 == 0 && ldc % 4 == 0, "K, lda, ldw % 8 and N, ldc % 4 required"}))
+    return rc;
   ASRX_REQUIRE(nj >= 1 && nj <= 3, "asrx_gemm_wn_ce: nj in 1..3");
-  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, nullptr, (int)ldc, nullptr, nullptr, (int)M, (int)N, (int)K,
-               1, 1, 1.f, 0.f, ACT_NONE, nullptr, nullptr, nullptr, nullptr, Zb, (float2*)part,
-               (int)((N + 128 * nj - 1) / (128 * nj))};
-  if (nj == 3) wn::launch_wr<3, false, false, true, true>(p, stream);
-  else if (nj == 2) wn::launch_wr<2, false, false, true, true>(p, stream);
-  else wn::launch_wr<1, false, false, true, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_ce");
+  wn::Params p = wide_params(A, lda, W, ldw, nullptr, ldc, nullptr, nullptr, M, N, K);
+  p.Cb = Zb;
+  p.ce_part = (float2*)part;
+  p.ce_ld = (int)((N + 128 * nj - 1) / (128 * nj));
+  return launched(run_wr<wn::Epi::CE>(p, 0, nj, 1, stream), "asrx_gemm_wn_ce");
 }
 
 // As asrx_gemm_wn_ce with the logits stored fp32 (Zf) and the statistics taken of the fp32 values.
 extern "C" int asrx_gemm_wn_ce_f32(const void* A, int64_t lda, const unsigned short* W, int64_t ldw, float* Zf,
                                int64_t ldc, float* part, int64_t M, int64_t N, int64_t K, int nj, hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_ce_f32: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)Zf & 15) == 0 &&
-                   ((uintptr_t)part & 7) == 0,
-               "asrx_gemm_wn_ce_f32: A/W 16-byte, Zf 16-byte, part 8-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && N % 4 == 0 && ldc % 4 == 0,
-               "asrx_gemm_wn_ce_f32: K, lda, ldw %% 8 and N, ldc %% 4 required");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_ce_f32: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn_ce_f32", A, 1, lda, W, ldw, M, N, K,
+                          {((uintptr_t)Zf & 15) == 0 && ((uintptr_t)part & 7) == 0,
+                           "A/W 16-byte, Zf 16-byte, part 8-byte aligned"},
+                          {N % 4 == 0 && ldc % 4 == 0, "K, lda, ldw % 8 and N, ldc % 4 required"}))
+    return rc;
   ASRX_REQUIRE(nj >= 1 && nj <= 3, "asrx_gemm_wn_ce_f32: nj in 1..3");
-  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, Zf, (int)ldc, nullptr, nullptr, (int)M, (int)N, (int)K,
-               1, 1, 1.f, 0.f, ACT_NONE, nullptr, nullptr, nullptr, nullptr, nullptr, (float2*)part,
-               (int)((N + 128 * nj - 1) / (128 * nj))};
-  if (nj == 3) wn::launch_wr<3, false, false, true, true>(p, stream);
-  else if (nj == 2) wn::launch_wr<2, false, false, true, true>(p, stream);
-  else wn::launch_wr<1, false, false, true, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_ce_f32");
+  wn::Params p = wide_params(A, lda, W, ldw, Zf, ldc, nullptr, nullptr, M, N, K);
+  p.ce_part = (float2*)part;
+  p.ce_ld = (int)((N + 128 * nj - 1) / (128 * nj));
+  return launched(run_wr<wn::Epi::CE>(p, 0, nj, 1, stream), "asrx_gemm_wn_ce_f32");
 }
 
 // Logits-free head (essentials.py:875-935 evaluation: model(...)["loss"] and torch.argmax(logits, -1);
@@ -222,24 +281,20 @@ extern "C" int asrx_gemm_wn_ce_f32(const void* A, int64_t lda, const unsigned sh
 extern "C" int asrx_gemm_wn_head(const void* A, int64_t lda, const unsigned short* W, int64_t ldw, float* part,
                                  const int64_t* labels, float* zlab, int64_t M, int64_t N, int64_t K, int nj,
                                  hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_head: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)part & 7) == 0,
-               "asrx_gemm_wn_head: A/W 16-byte, part 8-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % 8 == 0 && ldw % 8 == 0 && N % 4 == 0 && lda >= K,
-               "asrx_gemm_wn_head: K, lda, ldw %% 8, N %% 4 and lda >= K required");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_head: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn_head", A, 1, lda, W, ldw, M, N, K,
+                          {((uintptr_t)part & 7) == 0, "A/W 16-byte, part 8-byte aligned"},
+                          {N % 4 == 0 && lda >= K, "K, lda, ldw % 8, N % 4 and lda >= K required"}))
+    return rc;
   ASRX_REQUIRE(nj >= 1 && nj <= 3, "asrx_gemm_wn_head: nj in 1..3");
   ASRX_REQUIRE(!labels || zlab, "asrx_gemm_wn_head: labels need zlab");
   const int64_t nparts = (N + 128 * nj - 1) / (128 * nj);
-  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, nullptr, (int)N, nullptr, nullptr, (int)M, (int)N, (int)K,
-               1, 1, 1.f, 0.f, ACT_NONE, nullptr, nullptr, nullptr, nullptr, nullptr, (float2*)part, (int)nparts};
+  wn::Params p = wide_params(A, lda, W, ldw, nullptr, N, nullptr, nullptr, M, N, K);
+  p.ce_part = (float2*)part;
+  p.ce_ld = (int)nparts;
   p.hd_idx = reinterpret_cast<int*>(part + 2 * M * nparts);
   p.hd_labels = labels;
   p.hd_zlab = zlab;
-  if (nj == 3) wn::launch_wr<3, false, false, true, true, false, false, false, true>(p, stream);
-  else if (nj == 2) wn::launch_wr<2, false, false, true, true, false, false, false, true>(p, stream);
-  else wn::launch_wr<1, false, false, true, true, false, false, false, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_head");
+  return launched(run_wr<wn::Epi::Head>(p, 0, nj, 1, stream), "asrx_gemm_wn_head");
 }
 
 // Out projection with its residual add (model.py:578-580 x = x + attn(...).out): C = R + A W^T + bias, A, C
@@ -248,22 +303,16 @@ extern "C" int asrx_gemm_wn_head(const void* A, int64_t lda, const unsigned shor
 extern "C" int asrx_gemm_wn_res(const float* A, int64_t lda, const unsigned short* W, int64_t ldw, float* C, int64_t ldc,
                                 const float* bias, const float* R, int64_t ldr, int64_t M, int64_t N, int64_t K, int nj,
                                 hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_res: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0 &&
-                   ((uintptr_t)R & 15) == 0,
-               "asrx_gemm_wn_res: A/W/C/R must be 16-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % 4 == 0 && ldw % 8 == 0 && N % 4 == 0 && ldc % 4 == 0 && ldr % 4 == 0,
-               "asrx_gemm_wn_res: K, ldw %% 8; lda, N, ldc, ldr %% 4");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_res: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn_res", A, 0, lda, W, ldw, M, N, K,
+                          {((uintptr_t)C & 15) == 0 && ((uintptr_t)R & 15) == 0, "A/W/C/R must be 16-byte aligned"},
+                          {N % 4 == 0 && ldc % 4 == 0 && ldr % 4 == 0, "K, ldw % 8; lda, N, ldc, ldr % 4"}))
+    return rc;
   ASRX_REQUIRE(R && R != C, "asrx_gemm_wn_res: a residual input distinct from C is required");
   ASRX_REQUIRE(nj == 1 || nj == 3, "asrx_gemm_wn_res: nj 1 or 3");
-  wn::Params p{A, (int)lda, W, (int)ldw, C, (int)ldc, bias, nullptr, (int)M, (int)N, (int)K, 1, 1, 1.f, 0.f,
-               ACT_NONE, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, R, (int)ldr};
-  if (ws_on() && wn::ws_ok(p, false, ws_any())) wn::launch_ws<false, ACT_NONE, true, false>(p, stream);
-  else if (nj == 3 && p2_ok(p, 0, nj, 0)) wn::launch_p2_act<3, false, true>(p, stream);
-  else if (nj == 3) wn::launch_wr<3, false, false, false, false, true>(p, stream);
-  else wn::launch_wr<1, false, false, false, false, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_res");
+  wn::Params p = wide_params(A, lda, W, ldw, C, ldc, bias, nullptr, M, N, K);
+  p.Rres = R;
+  p.ldr = (int)ldr;
+  return launched(run_wide<wn::Epi::Res>(p, 0, nj, 0, stream), "asrx_gemm_wn_res");
 }
 
 // q / k projection with rotary fused (model.py:242-245 then 198-214, with the hd^-0.25 scale of model.py:303-304):
@@ -275,34 +324,22 @@ extern "C" int asrx_gemm_wn_rot(const void* A, int a_bf16, int64_t lda, const un
                                 float* C, float* Z, int64_t ldc, const float* bias, const float* m, const float* tab,
                                 int64_t L, int64_t hd, float scale, int64_t M, int64_t N, int64_t K, int nj,
                                 hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0 && L > 0, "asrx_gemm_wn_rot: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)C & 15) == 0 &&
-                   ((uintptr_t)Z & 15) == 0 && ((uintptr_t)tab & 15) == 0,
-               "asrx_gemm_wn_rot: A/W/C/Z/tab must be 16-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % (a_bf16 ? 8 : 4) == 0 && ldw % 8 == 0 && N % 4 == 0 && ldc % 4 == 0,
-               "asrx_gemm_wn_rot: K, ldw %% 8; lda %% 4 (8 bf16); N, ldc %% 4");
-  ASRX_REQUIRE(hd >= 4 && hd % 4 == 0 && N % hd == 0, "asrx_gemm_wn_rot: head dim %% 4, N %% hd");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_rot: operand spans >= 2^31 elements");
+  const bool heads = hd >= 4 && hd % 4 == 0 && N % hd == 0;
+  if (int rc = wide_check("asrx_gemm_wn_rot", A, a_bf16, lda, W, ldw, M, N, K,
+                          {((uintptr_t)C & 15) == 0 && ((uintptr_t)Z & 15) == 0 && ((uintptr_t)tab & 15) == 0,
+                           "A/W/C/Z/tab must be 16-byte aligned"},
+                          {N % 4 == 0 && ldc % 4 == 0, "K, ldw % 8; lda % 4 (8 bf16); N, ldc % 4"},
+                          L > 0 ? nullptr : "empty problem", heads ? nullptr : "head dim % 4, N % hd"))
+    return rc;
   ASRX_REQUIRE(m && tab, "asrx_gemm_wn_rot: row norms and angle table required");
   ASRX_REQUIRE(nj == 1 || nj == 3, "asrx_gemm_wn_rot: nj 1 or 3");
-  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, C, (int)ldc, bias, Z, (int)M, (int)N, (int)K, 1, 1, 1.f, 0.f,
-               ACT_NONE};
+  wn::Params p = wide_params(A, lda, W, ldw, C, ldc, bias, Z, M, N, K);
   p.rot_m = m;
   p.rot_tab = reinterpret_cast<const float2*>(tab);
   p.rot_L = (int)L;
   p.rot_half = (int)(hd / 2);
   p.rot_scale = scale;
-  // the same kernel choice as asrx_gemm_wn_ex: gemm_ws where it takes the shape, gemm_p2 where p2_ok (so fp32 A at
-  // >= 131072 rows and gemm variant 0 stay on gemm_wr), gemm_wr otherwise -- every form bit-identical
-  if (ws_on() && wn::ws_ok(p, a_bf16, ws_any())) a_bf16 ? wn::launch_ws<true, ACT_NONE, false, true>(p, stream)
-                                      : wn::launch_ws<false, ACT_NONE, false, true>(p, stream);
-  else if (nj == 3 && p2_ok(p, 0, nj, a_bf16)) a_bf16 ? wn::launch_p2<3, true, ACT_NONE, false, true>(p, stream)
-                                                   : wn::launch_p2<3, false, ACT_NONE, false, true>(p, stream);
-  else if (nj == 3) a_bf16 ? wn::launch_wr<3, false, false, true, false, false, false, true>(p, stream)
-                           : wn::launch_wr<3, false, false, false, false, false, false, true>(p, stream);
-  else a_bf16 ? wn::launch_wr<1, false, false, true, false, false, false, true>(p, stream)
-              : wn::launch_wr<1, false, false, false, false, false, false, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_rot");
+  return launched(run_wide<wn::Epi::Rot>(p, 0, nj, a_bf16, stream), "asrx_gemm_wn_rot");
 }
 
 // Backward of y = act(A W^T + bias) (act gelu / silu / sigmoid) without a stored pre-activation: the GEMM
@@ -312,21 +349,19 @@ extern "C" int asrx_gemm_wn_rot(const void* A, int a_bf16, int64_t lda, const un
 extern "C" int asrx_gemm_wn_gact(const void* A, int a_bf16, int64_t lda, const unsigned short* W, int64_t ldw,
                                  const float* bias, const float* G, int64_t ldg, unsigned short* gz, int64_t ldc,
                                  float* db, int64_t M, int64_t N, int64_t K, int act, int nj, hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_gact: empty problem");
-  ASRX_REQUIRE(nj == 3, "asrx_gemm_wn_gact: nj 3 only");
-  ASRX_REQUIRE(act == ACT_GELU || act == ACT_SILU || act == ACT_SIGMOID, "asrx_gemm_wn_gact: gelu/silu/sigmoid only");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0 && ((uintptr_t)G & 15) == 0 &&
-                   ((uintptr_t)gz & 7) == 0,
-               "asrx_gemm_wn_gact: A/W/G 16-byte, gz 8-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % (a_bf16 ? 8 : 4) == 0 && ldw % 8 == 0 && N % 4 == 0 && ldc % 4 == 0 &&
-                   ldg % 4 == 0,
-               "asrx_gemm_wn_gact: K, ldw %% 8; lda %% 4 (8 bf16); N, ldc, ldg %% 4");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_gact: operand spans >= 2^31 elements");
-  wn::Params p{(const float*)A, (int)lda, W, (int)ldw, nullptr, (int)ldc, bias, nullptr, (int)M, (int)N, (int)K, 1,
-               1, 1.f, 0.f, act, nullptr, nullptr, nullptr, nullptr, gz, nullptr, 0, nullptr, 0, G, (int)ldg, db};
-  if (a_bf16) wn::launch_wr<3, false, false, true, false, false, true>(p, stream);
-  else wn::launch_wr<3, false, false, false, false, false, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_gact");
+  const char* early = nj != 3 ? "nj 3 only"
+                      : act != ACT_GELU && act != ACT_SILU && act != ACT_SIGMOID ? "gelu/silu/sigmoid only" : nullptr;
+  if (int rc = wide_check("asrx_gemm_wn_gact", A, a_bf16, lda, W, ldw, M, N, K,
+                          {((uintptr_t)G & 15) == 0 && ((uintptr_t)gz & 7) == 0, "A/W/G 16-byte, gz 8-byte aligned"},
+                          {N % 4 == 0 && ldc % 4 == 0 && ldg % 4 == 0, "K, ldw % 8; lda % 4 (8 bf16); N, ldc, ldg % 4"},
+                          early))
+    return rc;
+  wn::Params p = wide_params(A, lda, W, ldw, nullptr, ldc, bias, nullptr, M, N, K, 1.f, 0.f, act);
+  p.Cb = gz;
+  p.G = G;
+  p.ldg = (int)ldg;
+  p.dB = db;
+  return launched(run_wr<wn::Epi::GAct>(p, 0, nj, a_bf16, stream), "asrx_gemm_wn_gact");
 }
 
 // asrx_gemm_wn restricted to the BM-row tiles listed in mtiles (n_mtiles entries, both on the device,
@@ -335,17 +370,12 @@ extern "C" int asrx_gemm_wn_rows(const float* A, int64_t lda, const unsigned sho
                                  int64_t ldc, const float* bias, float* Z, int64_t M, int64_t N, int64_t K,
                                  float alpha, float beta, int act, int nj, const int* mtiles, const int* n_mtiles,
                                  hipStream_t stream) {
-  ASRX_REQUIRE(M > 0 && N > 0 && K > 0, "asrx_gemm_wn_rows: empty problem");
-  ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0, "asrx_gemm_wn_rows: A/W must be 16-byte aligned");
-  ASRX_REQUIRE(K % 8 == 0 && lda % 4 == 0 && ldw % 8 == 0, "asrx_gemm_wn_rows: K%%8, lda%%4, ldw%%8 required");
-  ASRX_REQUIRE(M * lda < (1LL << 31) && N * ldw < (1LL << 31), "asrx_gemm_wn_rows: operand spans >= 2^31 elements");
+  if (int rc = wide_check("asrx_gemm_wn_rows", A, 0, lda, W, ldw, M, N, K)) return rc;
   ASRX_REQUIRE(mtiles && n_mtiles, "asrx_gemm_wn_rows: tile list required");
-  wn::Params p{A, (int)lda, W, (int)ldw, C, (int)ldc, bias, Z, (int)M, (int)N, (int)K, 1, 1, alpha, beta, act,
-               nullptr, nullptr, mtiles, n_mtiles};
-  if (nj == 3) wn::launch_wr<3, false>(p, stream);
-  else if (nj == 2) wn::launch_wr<2, false>(p, stream);
-  else wn::launch_wr<1, false>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_rows");
+  wn::Params p = wide_params(A, lda, W, ldw, C, ldc, bias, Z, M, N, K, alpha, beta, act);
+  p.mtiles = mtiles;
+  p.n_mtiles = n_mtiles;
+  return launched(run_wr<wn::Epi::Plain>(p, 0, nj, 0, stream), "asrx_gemm_wn_rows");
 }
 
 // The BM-row tiles of an M-row activation whose rows r belong to a sample b = r / L that is at MSheath
@@ -521,8 +551,9 @@ extern "C" int asrx_gemm_wn_router(const float* A, int64_t lda, const unsigned s
   ASRX_REQUIRE(((uintptr_t)A & 15) == 0 && ((uintptr_t)W1 & 15) == 0, "asrx_gemm_wn_router: A/W must be 16-byte aligned");
   ASRX_REQUIRE(K % 8 == 0 && lda % 4 == 0 && ldw % 8 == 0, "asrx_gemm_wn_router: K%%8, lda%%4, ldw%%8 required");
   ASRX_REQUIRE(M * lda < (1LL << 31), "asrx_gemm_wn_router: operand spans >= 2^31 elements");
-  wn::Params p{A, (int)lda, W1, (int)ldw, hpre, (int)ldc, b1, nullptr, (int)M, (int)N, (int)K, 1, 1, 1.f, 0.f,
-               ACT_NONE, W2, logits};
+  wn::Params p = wide_params(A, lda, W1, ldw, hpre, ldc, b1, nullptr, M, N, K);
+  p.W2 = W2;
+  p.R = logits;
   const bool r64 = N == 64 && K == 64 && W2 && (g_wide_variant & 16) == 0 && ldw % 8 == 0 &&
                    (!hpre || (ldc % 4 == 0 && ((uintptr_t)hpre & 15) == 0));
   if (r64) {
@@ -536,8 +567,7 @@ extern "C" int asrx_gemm_wn_router(const float* A, int64_t lda, const unsigned s
     const int64_t groups = (M + 15) / 16;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)cus * 8));
     wn::router64_kernel<<<grid, 256, 0, stream>>>(p);
-  } else if (N <= 128) wn::launch_wr<1, false, true>(p, stream);
-  else if (N <= 256) wn::launch_wr<2, false, true>(p, stream);
-  else wn::launch_wr<3, false, true>(p, stream);
-  ASRX_LAUNCHED("asrx_gemm_wn_router");
+    ASRX_LAUNCHED("asrx_gemm_wn_router");
+  }
+  return launched(run_wr<wn::Epi::Router>(p, 0, N <= 128 ? 1 : N <= 256 ? 2 : 3, 0, stream), "asrx_gemm_wn_router");
 }

@@ -33,6 +33,21 @@ constexpr int A_BYTES = BM * BK * 4;  // 16 KB fp32
 
 static __device__ __attribute__((aligned(16))) float zero_page[4];
 
+// The epilogue a wide-GEMM instantiation carries (gemm_wr_kernel: all of them; gemm_p2_kernel / gemm_ws_kernel:
+// Plain, Res, Rot).  They exclude each other; Head is the CE statistics without the logits store.
+enum class Epi {
+  Plain,   // act(alpha A W^T + beta C + bias), runtime act; fp32 or bf16 (Params::Cb) output, optional Z
+  Router,  // AbbyNormal router (Params::W2, R): epilogue_router
+  CE,      // tied logits with cross-entropy statistics (Params::ce_part): epilogue_ce
+  Head,    // logits-free head (Params::hd_*): epilogue_head
+  Res,     // + residual input (Params::Rres), act none
+  GAct,    // activation gradient (Params::G, dB): epilogue_gact
+  Rot      // rotary on the product (Params::rot_*), act none
+};
+// readable values for the two flags that stay bool: where A's rows come from and how A is stored
+constexpr bool ROWS = false, CONV3 = true;  // CONV: plain rows / the implicit k3 im2col
+constexpr bool F32A = false, BF16A = true;  // ABF: A stored fp32 / bf16
+
 struct Params {
   const float* A;
   int lda;
@@ -56,7 +71,7 @@ struct Params {
   // bf16 output (gemm_wr_kernel): when non-null, act(v) is written here as bf16 instead of to C
   // (an activation whose only consumers are GEMM operands -- they round it to bf16 anyway); beta = 0
   unsigned short* Cb;
-  // fused cross-entropy statistics (gemm_wr_kernel<..., CE>): the tied-logits GEMM (model.py:629) writes
+  // fused cross-entropy statistics (gemm_wr_kernel<..., Epi::CE>): the tied-logits GEMM (model.py:629) writes
   // the logits bf16 (Cb) and, per row and BN-column tile, the (max, sum exp(z - max)) of the tile's
   // bf16-rounded logits into ce_part[row * ce_ld + tile] (float2), so the cross entropy never re-reads
   // the logits for its log-sum-exp (asrx_ce_part_fwd merges the partials)
@@ -66,14 +81,14 @@ struct Params {
   // around an out projection (model.py:578-580 x = x + attn(...)) without a separate add pass
   const float* Rres;
   int ldr;
-  // activation-gradient epilogue (gemm_wr_kernel<..., GA>): the GEMM recomputes the pre-activation
+  // activation-gradient epilogue (gemm_wr_kernel<..., Epi::GAct>): the GEMM recomputes the pre-activation
   // z = alpha A W^T + bias of a Linear + act whose forward did not keep it, and stores
   // gz = bf16(G * act'(z)) to Cb (G: the output gradient, fp32, row stride ldg) with the bias gradient's
   // column sums of gz added into dB (nullable) -- the backward never reads a stored z
   const float* G;
   int ldg;
   float* dB;
-  // rotary epilogue (ROT instantiations, act none, fp32 C): the q / k projection's rotary (model.py:198-214)
+  // rotary epilogue (Epi::Rot instantiations, act none, fp32 C): the q / k projection's rotary (model.py:198-214)
   // applied to the product before it is stored -- C = rot(alpha A W^T + bias), the pairs (2j, 2j+1) of each
   // head times polar(rot_scale * rot_m[row], angle(row % rot_L, j)) from the (cos, sin) table rot_tab
   // ((positions, rot_half) float2, asrx_rotary_table); Z, when non-null, receives the unrotated product
@@ -82,7 +97,7 @@ struct Params {
   const float2* rot_tab;
   int rot_L, rot_half;
   float rot_scale;
-  // logits-free head (gemm_wr_kernel<..., CE, HEAD>; essentials.py:875-935 evaluation, model.py:691-699 greedy
+  // logits-free head (gemm_wr_kernel<..., Epi::Head>; essentials.py:875-935 evaluation, model.py:691-699 greedy
   // step): no logits are stored -- per row and BN-column tile the (max, sum exp(z - max)) of the tile's fp32
   // logits go to ce_part as in the CE variant and the column of that max (lowest among equals) to
   // hd_idx[row * ce_ld + tile]; with hd_labels (nullable) the logit of each row's label goes to hd_zlab[row]
@@ -208,9 +223,11 @@ __device__ __forceinline__ float4 rot_apply(const Params& p, float4 x, int row, 
                      mm * (x.z * t.w + x.w * t.z));
 }
 
-template <int NJ, int ACT, bool RES = false, bool ROT = false>
+template <int NJ, int ACT, Epi EPI = Epi::Plain>
 __device__ __forceinline__ void epilogue_lds(const Params& p, f32x4 (&acc)[4][2 * NJ], const float* bsl, int m0,
                                              int n0, int wm, int wn, int lr, int lk, float* ep) {
+  constexpr bool RES = EPI == Epi::Res, ROT = EPI == Epi::Rot;
+  static_assert(EPI == Epi::Plain || ((RES || ROT) && ACT == ACT_NONE), "plain, or residual / rotary without activation");
   constexpr int NT = 2 * NJ, W = EpLds<NJ>::W, LD = EpLds<NJ>::LD, W4 = W / 4;
   constexpr int PER = 16 * W4 / 64;  // float4 per lane per slice
   static_assert((16 * W4) % 64 == 0, "slice must split evenly over the wave");
@@ -251,14 +268,14 @@ __device__ __forceinline__ void epilogue_lds(const Params& p, f32x4 (&acc)[4][2 
         const float4 o = *reinterpret_cast<const float4*>(dst);
         x.x += p.beta * o.x; x.y += p.beta * o.y; x.z += p.beta * o.z; x.w += p.beta * o.w;
       }
-      if constexpr (RES) {  // the residual add of an out projection (RES instantiations only)
+      if constexpr (RES) {  // the residual add of an out projection (Epi::Res instantiations only)
         const float4 o = *reinterpret_cast<const float4*>(p.Rres + (int64_t)row * p.ldr + col);
         x.x += o.x; x.y += o.y; x.z += o.z; x.w += o.w;
       }
       if (p.Z)
         __builtin_nontemporal_store(f32x4{x.x, x.y, x.z, x.w},
                                     reinterpret_cast<f32x4*>(p.Z + (int64_t)row * p.ldc + col));
-      if constexpr (ROT) x = rot_apply(p, x, row, col);  // act none (ROT instantiations)
+      if constexpr (ROT) x = rot_apply(p, x, row, col);  // act none (Epi::Rot instantiations)
       __builtin_nontemporal_store(f32x4{act_t<ACT>(x.x), act_t<ACT>(x.y), act_t<ACT>(x.z), act_t<ACT>(x.w)},
                                   reinterpret_cast<f32x4*>(dst));
     }
@@ -588,7 +605,6 @@ __device__ __forceinline__ void epilogue_router(const Params& p, f32x4 (&acc)[4]
 #ifndef WR_DEPTH
 #define WR_DEPTH 3  // register stages in flight (k-steps of prefetch)
 #endif
-// DEP (template): register stages, 0 = WR_DEPTH
 
 // ABF: A is stored bf16 (M x K, lda in elements): one 16-byte chunk of 8 k per thread and k-step
 // (row t/4, k chunk t%4), already in the image's element type -- half the bytes, no conversion
@@ -850,10 +866,29 @@ __device__ __forceinline__ void wr_load64_fast(const Params& p, WrStage64<ABF>& 
   for (int i = 0; i < 2; ++i) st.b[i] = *reinterpret_cast<const u32x4*>(W + (o.w[i] + kw));
 }
 
-template <int NJ, bool CONV, bool RT, int DEP = 0, bool ABF = false, bool CE = false, bool RES = false,
-          bool GA = false, bool ROT = false, bool HEAD = false>
+// The (NJ, CONV, ABF, EPI) combinations of gemm_wr_kernel: those an entry point asks for, each explicitly
+// instantiated in one gemm_wr_*.hip unit (the list at the end of this file says the same, instance by instance).
+// Any other combination fails to compile, in the kernel's static_assert.
+constexpr bool wr_built(int nj, bool conv, bool abf, Epi e) {
+  if (nj < 1 || nj > 3) return false;
+  switch (e) {
+    case Epi::Plain: return true;
+    case Epi::Router: return !conv && !abf;
+    case Epi::CE: return !conv && abf;
+    case Epi::Head: return !conv && abf;
+    case Epi::Res: return !conv && !abf && nj != 2;
+    case Epi::GAct: return !conv && nj == 3;
+    case Epi::Rot: return !conv && nj != 2;
+  }
+  return false;
+}
+
+template <int NJ, bool CONV, bool ABF, Epi EPI>
 __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) {  // ntiles: all tiles
+  constexpr bool RT = EPI == Epi::Router, HEAD = EPI == Epi::Head, CE = EPI == Epi::CE || HEAD;
+  constexpr bool RES = EPI == Epi::Res, GA = EPI == Epi::GAct, ROT = EPI == Epi::Rot;
   static_assert(!HEAD || (CE && ABF), "the head epilogue is a variant of the bf16-A CE instantiation");
+  static_assert(wr_built(NJ, CONV, ABF, EPI), "not a gemm_wr_kernel instantiation (wr_built)");
   typedef Cfg<NJ> CF;
   constexpr int BN = CF::BN, NT = 2 * NJ, BNR = CF::BNR;
   constexpr bool K64 = NJ == 1 && !CONV;  // 64-deep k-steps (WrStage64)
@@ -977,7 +1012,7 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) 
 
   // stage register sets are named variables (an array, even constant-indexed after unrolling,
   // ends up in scratch)
-  constexpr int DEPTH = DEP ? DEP : WR_DEPTH;
+  constexpr int DEPTH = WR_DEPTH;
   static_assert(DEPTH >= 3 && DEPTH <= 5, "stage sets are written out for depths 3..5");
   Stg st0, st1, st2, st3, st4;  // st3 / st4 unused (eliminated) below depth 4 / 5
   load(st0, S > 0);
@@ -1059,9 +1094,9 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) 
       } else if constexpr (CE) {
         epilogue_ce<NJ>(p, acc, m0, n0, wm, wn, lr, lk, ep, reinterpret_cast<float2*>(red));
       } else if constexpr (RES) {  // act none, vec_ok (checked by the launcher)
-        epilogue_lds<NJ, ACT_NONE, true>(p, acc, bsl, m0, n0, wm, wn, lr, lk, ep);
+        epilogue_lds<NJ, ACT_NONE, Epi::Res>(p, acc, bsl, m0, n0, wm, wn, lr, lk, ep);
       } else if constexpr (ROT) {  // act none, fp32 C, vec_ok (checked by the launcher)
-        epilogue_lds<NJ, ACT_NONE, false, true>(p, acc, bsl, m0, n0, wm, wn, lr, lk, ep);
+        epilogue_lds<NJ, ACT_NONE, Epi::Rot>(p, acc, bsl, m0, n0, wm, wn, lr, lk, ep);
       } else if constexpr (GA) {  // gelu / silu / sigmoid (checked by the launcher)
         switch (p.act) {
           case ACT_GELU: epilogue_gact<NJ, ACT_GELU>(p, acc, bsl, m0, n0, wm, wn, lr, lk, ep); break;
@@ -1110,18 +1145,14 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_wr_kernel(Params p, int ntiles) 
   }
 }
 
-// Register pipeline depth per instantiation (0 = WR_DEPTH = 3).  A bf16-stored A halves a k-step's A slab,
-// but a deeper pipeline for it measured no faster on the 192k-row launches (166 us at 3 and at 4 k-steps)
+// Register pipeline depth (WR_DEPTH = 3, one value for every instantiation).  A bf16-stored A halves a k-step's
+// A slab, but a deeper pipeline for it measured no faster on the 192k-row launches (166 us at 3 and at 4 k-steps)
 // and slower on the 8192-row ones (28 -> 35 us; depth 5 spills): the bf16-A kernel is not bound by the A
 // bytes in flight (profiles/r03_kernel_stats_*.csv)
-template <bool ABF>
-constexpr int wr_dep() { return 0; }
-
-template <int NJ, bool CONV, bool RT = false, bool ABF = false, bool CE = false, bool RES = false, bool GA = false,
-          bool ROT = false, bool HEAD = false>
+template <int NJ, bool CONV, bool ABF, Epi EPI>
 void launch_wr(const Params& p, hipStream_t s) {
   static int resident = 0;
-  const void* fn = (const void*)gemm_wr_kernel<NJ, CONV, RT, wr_dep<ABF>(), ABF, CE, RES, GA, ROT, HEAD>;
+  const void* fn = (const void*)gemm_wr_kernel<NJ, CONV, ABF, EPI>;
   if (!resident) {
     int per_cu = 0, dev = 0, cus = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NTHR, 0);
@@ -1131,49 +1162,46 @@ void launch_wr(const Params& p, hipStream_t s) {
   }
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + Cfg<NJ>::BN - 1) / Cfg<NJ>::BN);
   const int grid = std::min(tiles, resident);
-  // a 5-deep pipeline (DEP = 5) for the one-wave 8192-row text-side launches measured 32.4 us vs
+  // a 5-deep pipeline (WR_DEPTH = 5) for the one-wave 8192-row text-side launches measured 32.4 us vs
   // 30.1 us at depth 3 (profiles/r02_bench_v8_kernel_stats.csv): their time is not load latency
-  gemm_wr_kernel<NJ, CONV, RT, wr_dep<ABF>(), ABF, CE, RES, GA, ROT, HEAD><<<grid, NTHR, 0, s>>>(p, tiles);
+  gemm_wr_kernel<NJ, CONV, ABF, EPI><<<grid, NTHR, 0, s>>>(p, tiles);
 }
 
 }  // namespace wn
 }  // namespace asrx
 
-// Every instantiation lives in one of gemm_wr_i{1,2,3}.hip (compiled in parallel); other units only
-// declare them.
-#ifndef ASRX_WR_INSTANTIATE
-#define ASRX_WR_DECL(NJ, CONV, RT, ABF) extern template void asrx::wn::launch_wr<NJ, CONV, RT, ABF>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_CE(NJ) extern template void asrx::wn::launch_wr<NJ, false, false, true, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_RES(NJ) extern template void asrx::wn::launch_wr<NJ, false, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_GA(NJ, ABF) extern template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_ROT(NJ, ABF) extern template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_HEAD(NJ) extern template void asrx::wn::launch_wr<NJ, false, false, true, true, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
+// Every instantiation is compiled in exactly one gemm_wr_*.hip unit (one unit per 384-column kernel or small
+// group, so the build compiles them in parallel): such a unit defines ASRX_WR_INSTANTIATE and lists its
+// instances with ASRX_WR_INST; every other unit only declares them, through the list below.  A new instance
+// is one line here, the same line in its unit, and its case in wr_built.
+#ifdef ASRX_WR_INSTANTIATE
+#define ASRX_WR_EXTERN
 #else
-#define ASRX_WR_DECL(NJ, CONV, RT, ABF) template void asrx::wn::launch_wr<NJ, CONV, RT, ABF>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_CE(NJ) template void asrx::wn::launch_wr<NJ, false, false, true, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_RES(NJ) template void asrx::wn::launch_wr<NJ, false, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_GA(NJ, ABF) template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_ROT(NJ, ABF) template void asrx::wn::launch_wr<NJ, false, false, ABF, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WR_DECL_HEAD(NJ) template void asrx::wn::launch_wr<NJ, false, false, true, true, false, false, false, true>(const asrx::wn::Params&, hipStream_t);
+#define ASRX_WR_EXTERN extern
 #endif
-#define ASRX_WR_SET(NJ) ASRX_WR_DECL(NJ, false, false, false) ASRX_WR_DECL(NJ, true, false, false) \
-  ASRX_WR_DECL(NJ, false, false, true) ASRX_WR_DECL(NJ, true, false, true) ASRX_WR_DECL(NJ, false, true, false)
+#define ASRX_WR_INST(NJ, CONV, ABF, EPI)                                                                    \
+  ASRX_WR_EXTERN template void asrx::wn::launch_wr<NJ, asrx::wn::CONV, asrx::wn::ABF, asrx::wn::Epi::EPI>( \
+      const asrx::wn::Params&, hipStream_t);
+// the plain and router instances of one tile width (gemm_wr_i1.hip, gemm_wr_i2.hip; gemm_wr_i3_{1..5}.hip one each)
+#define ASRX_WR_SET(NJ)                                                                                  \
+  ASRX_WR_INST(NJ, ROWS, F32A, Plain) ASRX_WR_INST(NJ, CONV3, F32A, Plain) ASRX_WR_INST(NJ, ROWS, BF16A, Plain) \
+  ASRX_WR_INST(NJ, CONV3, BF16A, Plain) ASRX_WR_INST(NJ, ROWS, F32A, Router)
 #ifndef ASRX_WR_INSTANTIATE
 ASRX_WR_SET(1)
 ASRX_WR_SET(2)
 ASRX_WR_SET(3)
-ASRX_WR_DECL_CE(1)
-ASRX_WR_DECL_CE(2)
-ASRX_WR_DECL_CE(3)
-ASRX_WR_DECL_RES(1)
-ASRX_WR_DECL_RES(3)
-ASRX_WR_DECL_GA(3, false)
-ASRX_WR_DECL_GA(3, true)
-ASRX_WR_DECL_ROT(1, true)
-ASRX_WR_DECL_ROT(1, false)
-ASRX_WR_DECL_ROT(3, true)
-ASRX_WR_DECL_ROT(3, false)
-ASRX_WR_DECL_HEAD(1)
-ASRX_WR_DECL_HEAD(2)
-ASRX_WR_DECL_HEAD(3)
+ASRX_WR_INST(1, ROWS, BF16A, CE)
+ASRX_WR_INST(2, ROWS, BF16A, CE)
+ASRX_WR_INST(3, ROWS, BF16A, CE)
+ASRX_WR_INST(1, ROWS, F32A, Res)
+ASRX_WR_INST(3, ROWS, F32A, Res)
+ASRX_WR_INST(3, ROWS, F32A, GAct)
+ASRX_WR_INST(3, ROWS, BF16A, GAct)
+ASRX_WR_INST(1, ROWS, BF16A, Rot)
+ASRX_WR_INST(1, ROWS, F32A, Rot)
+ASRX_WR_INST(3, ROWS, BF16A, Rot)
+ASRX_WR_INST(3, ROWS, F32A, Rot)
+ASRX_WR_INST(1, ROWS, BF16A, Head)
+ASRX_WR_INST(2, ROWS, BF16A, Head)
+ASRX_WR_INST(3, ROWS, BF16A, Head)
 #endif

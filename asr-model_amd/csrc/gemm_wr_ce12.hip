@@ -3,5 +3,5 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL_CE(1)
-ASRX_WR_DECL_CE(2)
+ASRX_WR_INST(1, ROWS, BF16A, CE)
+ASRX_WR_INST(2, ROWS, BF16A, CE)

@@ -3,4 +3,4 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL_CE(3)
+ASRX_WR_INST(3, ROWS, BF16A, CE)

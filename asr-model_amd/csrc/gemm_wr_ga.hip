@@ -4,5 +4,5 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL_GA(3, false)
-ASRX_WR_DECL_GA(3, true)
+ASRX_WR_INST(3, ROWS, F32A, GAct)
+ASRX_WR_INST(3, ROWS, BF16A, GAct)

@@ -3,4 +3,4 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL_HEAD(2)
+ASRX_WR_INST(2, ROWS, BF16A, Head)

@@ -3,4 +3,4 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL(3, false, false, true)
+ASRX_WR_INST(3, ROWS, BF16A, Plain)

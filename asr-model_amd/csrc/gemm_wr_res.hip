@@ -3,5 +3,5 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL_RES(1)
-ASRX_WR_DECL_RES(3)
+ASRX_WR_INST(1, ROWS, F32A, Res)
+ASRX_WR_INST(3, ROWS, F32A, Res)

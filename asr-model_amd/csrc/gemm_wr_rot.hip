@@ -5,7 +5,7 @@
 #define ASRX_WR_INSTANTIATE
 #include "gemm_wr.h"
 
-ASRX_WR_DECL_ROT(1, true)
-ASRX_WR_DECL_ROT(1, false)
-ASRX_WR_DECL_ROT(3, true)
-ASRX_WR_DECL_ROT(3, false)
+ASRX_WR_INST(1, ROWS, BF16A, Rot)
+ASRX_WR_INST(1, ROWS, F32A, Rot)
+ASRX_WR_INST(3, ROWS, BF16A, Rot)
+ASRX_WR_INST(3, ROWS, F32A, Rot)

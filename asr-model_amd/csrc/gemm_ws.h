@@ -86,8 +86,14 @@ __device__ __forceinline__ void stage_store(const Stage<ABF>& st, char* At) {
 }  // namespace ws
 
 // grid = nS * lanes workgroups: slice s = rank % nS, row tiles rank / nS + i * lanes
-template <bool ABF, int ACT, bool RES, bool ROT>
+// The (ABF, EPI) combinations of gemm_ws_kernel the entry points use (every activation for Epi::Plain, none
+// otherwise), instantiated in the gemm_ws_*.hip units; any other fails to compile.
+constexpr bool ws_built(bool abf, Epi e) { return e == Epi::Plain || e == Epi::Rot || (e == Epi::Res && !abf); }
+
+template <bool ABF, int ACT, Epi EPI>
 __global__ __launch_bounds__(ws::WTHR, 1) void gemm_ws_kernel(Params p, int nS, int lanes) {
+  static_assert(ws_built(ABF, EPI), "not a gemm_ws_kernel instantiation (ws_built)");
+  static_assert(EPI == Epi::Plain || ACT == ACT_NONE, "the residual and rotary epilogues take no activation");
   using namespace ws;
   constexpr int KS = WsCfg<ABF>::KS, CH = WsCfg<ABF>::CH, NBUF = WsCfg<ABF>::NBUF, DEPTH = WsCfg<ABF>::DEPTH;
   constexpr bool PIPE = WsCfg<ABF>::PIPE;
@@ -219,7 +225,7 @@ __global__ __launch_bounds__(ws::WTHR, 1) void gemm_ws_kernel(Params p, int nS, 
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Fc.b[nt], Fc.a[mt], acc[mt][nt], 0, 0, 0);
       if (++ekk == nk) {
         const int m0 = (lane0 + ej * lanes) * BM;
-        epilogue_lds<1, ACT, RES, ROT>(p, acc, bias_s, m0, n0, wm, wn, lr, lk, ep);
+        epilogue_lds<1, ACT, EPI>(p, acc, bias_s, m0, n0, wm, wn, lr, lk, ep);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -283,7 +289,7 @@ __global__ __launch_bounds__(ws::WTHR, 1) void gemm_ws_kernel(Params p, int nS, 
     if (t + 1 < S) ws::stage_store<ABF>(nxt, a_img[(t + 1) & 1]);
     if (++ekk == nk) {
       const int m0 = (lane0 + ej * lanes) * BM;
-      epilogue_lds<1, ACT, RES, ROT>(p, acc, bias_s, m0, n0, wm, wn, lr, lk, ep);
+      epilogue_lds<1, ACT, EPI>(p, acc, bias_s, m0, n0, wm, wn, lr, lk, ep);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -326,7 +332,7 @@ inline bool ws_ok(const Params& p, bool a_bf16, bool any_shape = false) {
          (any_shape || (a_bf16 ? p.N >= 768 : p.N <= 768));
 }
 
-template <bool ABF, int ACT, bool RES, bool ROT>
+template <bool ABF, int ACT, Epi EPI>
 void launch_ws(const Params& p, hipStream_t s) {
   static int cus = 0;
   if (!cus) {
@@ -338,34 +344,40 @@ void launch_ws(const Params& p, hipStream_t s) {
   const int nS = (p.N + ws::BN - 1) / ws::BN;
   const int nM = (p.M + BM - 1) / BM;
   const int lanes = std::max(1, std::min(cus / nS, nM));  // row lanes per slice: one resident workgroup per CU
-  gemm_ws_kernel<ABF, ACT, RES, ROT><<<nS * lanes, ws::WTHR, 0, s>>>(p, nS, lanes);
+  gemm_ws_kernel<ABF, ACT, EPI><<<nS * lanes, ws::WTHR, 0, s>>>(p, nS, lanes);
 }
 
-template <bool ABF>
+// dispatch over the activation (runtime act -> template); the residual and rotary epilogues have none
+template <bool ABF, Epi EPI>
 void launch_ws_act(const Params& p, hipStream_t s) {
-  switch (p.act) {
-    case ACT_GELU: launch_ws<ABF, ACT_GELU, false, false>(p, s); break;
-    case ACT_SILU: launch_ws<ABF, ACT_SILU, false, false>(p, s); break;
-    case ACT_SIGMOID: launch_ws<ABF, ACT_SIGMOID, false, false>(p, s); break;
-    case ACT_RELU: launch_ws<ABF, ACT_RELU, false, false>(p, s); break;
-    default: launch_ws<ABF, ACT_NONE, false, false>(p, s); break;
+  if constexpr (EPI != Epi::Plain) {
+    launch_ws<ABF, ACT_NONE, EPI>(p, s);
+  } else {
+    switch (p.act) {
+      case ACT_GELU: launch_ws<ABF, ACT_GELU, EPI>(p, s); break;
+      case ACT_SILU: launch_ws<ABF, ACT_SILU, EPI>(p, s); break;
+      case ACT_SIGMOID: launch_ws<ABF, ACT_SIGMOID, EPI>(p, s); break;
+      case ACT_RELU: launch_ws<ABF, ACT_RELU, EPI>(p, s); break;
+      default: launch_ws<ABF, ACT_NONE, EPI>(p, s); break;
+    }
   }
 }
 
 }  // namespace wn
 }  // namespace asrx
 
-#ifndef ASRX_WS_INSTANTIATE
-#define ASRX_WS_DECL_ACT(ABF) extern template void asrx::wn::launch_ws_act<ABF>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WS_DECL(ABF, RES, ROT) \
-  extern template void asrx::wn::launch_ws<ABF, asrx::ACT_NONE, RES, ROT>(const asrx::wn::Params&, hipStream_t);
-ASRX_WS_DECL_ACT(true)
-ASRX_WS_DECL_ACT(false)
-ASRX_WS_DECL(false, true, false)
-ASRX_WS_DECL(true, false, true)
-ASRX_WS_DECL(false, false, true)
+// As gemm_wr.h: a gemm_ws_*.hip unit defines ASRX_WS_INSTANTIATE and lists its instances; other units declare.
+#ifdef ASRX_WS_INSTANTIATE
+#define ASRX_WS_EXTERN
 #else
-#define ASRX_WS_DECL_ACT(ABF) template void asrx::wn::launch_ws_act<ABF>(const asrx::wn::Params&, hipStream_t);
-#define ASRX_WS_DECL(ABF, RES, ROT) \
-  template void asrx::wn::launch_ws<ABF, asrx::ACT_NONE, RES, ROT>(const asrx::wn::Params&, hipStream_t);
+#define ASRX_WS_EXTERN extern
+#endif
+#define ASRX_WS_INST(ABF, EPI) \
+  ASRX_WS_EXTERN template void asrx::wn::launch_ws_act<asrx::wn::ABF, asrx::wn::Epi::EPI>(const asrx::wn::Params&, hipStream_t);
+#ifndef ASRX_WS_INSTANTIATE
+ASRX_WS_INST(BF16A, Plain)
+ASRX_WS_INST(F32A, Plain)
+ASRX_WS_INST(F32A, Res)
+ASRX_WS_INST(BF16A, Rot)
+ASRX_WS_INST(F32A, Rot)
 #endif

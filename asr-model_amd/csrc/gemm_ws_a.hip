@@ -3,4 +3,4 @@
 #define ASRX_WS_INSTANTIATE
 #include "gemm_ws.h"
 
-ASRX_WS_DECL_ACT(true)
+ASRX_WS_INST(BF16A, Plain)

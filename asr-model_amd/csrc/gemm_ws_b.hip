@@ -3,4 +3,4 @@
 #define ASRX_WS_INSTANTIATE
 #include "gemm_ws.h"
 
-ASRX_WS_DECL_ACT(false)
+ASRX_WS_INST(F32A, Plain)

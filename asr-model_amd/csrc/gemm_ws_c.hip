@@ -3,6 +3,6 @@
 #define ASRX_WS_INSTANTIATE
 #include "gemm_ws.h"
 
-ASRX_WS_DECL(false, true, false)
-ASRX_WS_DECL(true, false, true)
-ASRX_WS_DECL(false, false, true)
+ASRX_WS_INST(F32A, Res)
+ASRX_WS_INST(BF16A, Rot)
+ASRX_WS_INST(F32A, Rot)
