@@ -381,6 +381,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(
 using namespace asrx;
 
 static bool attn_ok(const int64_t* st) { return st[0] % 4 == 0 && st[1] % 4 == 0 && st[2] % 4 == 0; }
+// a bf16-stored q / k / v / dO is read 8 elements (16 bytes) at a time (attn_mf.hip stage_load, row_frags): with
+// the 16-byte base every such load is naturally aligned only when the strides are multiples of 8 elements
+static bool attn_ok8(const int64_t* st) { return st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0; }
 
 // Strides are passed as int64[3] = {batch, seq, head} in elements; the head-dim stride must be 1.
 namespace asrx {
@@ -428,6 +431,8 @@ extern "C" int asrx_attn_fwd2(int prec, int io, const void* q_, const int64_t* s
   ASRX_REQUIRE(io == 0 || prec == PREC_BF16, "attention: bf16 storage (io %d) is a bf16-mode layout", io);
   ASRX_REQUIRE(hd == 64 || hd == 128, "attention: head dim %ld unsupported (64 or 128)", (long)hd);
   ASRX_REQUIRE(attn_ok(sq) && attn_ok(sk) && attn_ok(sv) && attn_ok(so), "attention: strides must be multiples of 4");
+  ASRX_REQUIRE(!(io & 1) || (attn_ok8(sq) && attn_ok8(sk) && attn_ok8(sv)),
+               "attention: strides of bf16-stored operands must be multiples of 8");
   ASRX_REQUIRE(H < 65536 && B < 65536, "attention: grid too large");
   if (B * H * Lq == 0) return 0;
   ASRX_REQUIRE(Lk > 0, "attention: empty key sequence");
@@ -464,11 +469,18 @@ extern "C" int asrx_attn_bwd2(int prec, int io, const void* q_, const int64_t* s
   ASRX_REQUIRE(io == 0 || prec == PREC_BF16, "attention backward: bf16 storage (io %d) is a bf16-mode layout", io);
   ASRX_REQUIRE(prec == PREC_F32 || prec == PREC_BF16, "attention backward: precision %d (fp8 is forward only)", prec);
   ASRX_REQUIRE(hd == 64 || hd == 128, "attention: head dim %ld unsupported (64 or 128)", (long)hd);
-  ASRX_REQUIRE(attn_ok(sq) && attn_ok(sk) && attn_ok(sv) && attn_ok(sd) && attn_ok(sdq) && attn_ok(sdk) &&
-                   attn_ok(sdv),
+  ASRX_REQUIRE(attn_ok(sq) && attn_ok(sk) && attn_ok(sv) && attn_ok(so) && attn_ok(sd) && attn_ok(sdq) &&
+                   attn_ok(sdk) && attn_ok(sdv),
                "attention: strides must be multiples of 4");
+  ASRX_REQUIRE((!(io & 1) || (attn_ok8(sq) && attn_ok8(sk) && attn_ok8(sv))) && (!(io & 4) || attn_ok8(sd)),
+               "attention: strides of bf16-stored operands must be multiples of 8");
+  ASRX_REQUIRE(H < 65536 && B < 65536, "attention: grid too large");  // the fp32 kernels launch dim3(., H, B)
   if (B * H * Lq == 0) return 0;
   ASRX_REQUIRE(Lk > 0, "attention: empty key sequence");
+  // every check stands ahead of the first launch (Delta): a rejected call has launched nothing
+  const bool al16 = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dO | (uintptr_t)dq | (uintptr_t)dk |
+                       (uintptr_t)dv) & 15) == 0;
+  ASRX_REQUIRE(prec == PREC_F32 || al16, "attention backward: bf16 mode needs 16-byte aligned tensors");
   AttnStrides Sq{sq[0], sq[1], sq[2]}, Sk{sk[0], sk[1], sk[2]}, Sv{sv[0], sv[1], sv[2]}, So{so[0], so[1], so[2]};
   AttnStrides Sd{sd[0], sd[1], sd[2]}, Sdq{sdq[0], sdq[1], sdq[2]}, Sdk{sdk[0], sdk[1], sdk[2]},
       Sdv{sdv[0], sdv[1], sdv[2]};
@@ -494,9 +506,6 @@ extern "C" int asrx_attn_bwd2(int prec, int io, const void* q_, const int64_t* s
     }
   }
 #undef ASRX_DL
-  const bool al16 = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dO | (uintptr_t)dq | (uintptr_t)dk |
-                       (uintptr_t)dv) & 15) == 0;
-  ASRX_REQUIRE(prec == PREC_F32 || al16, "attention backward: bf16 mode needs 16-byte aligned tensors");
   if (prec == PREC_BF16)
     attn_bwd_mf(io, q, sq, k, sk, v, sv, dO, sd, lse, delta_ws, dq, sdq, dk, sdk, dv, sdv, B, H, Lq, Lk, hd, causal,
                 scale, stream);

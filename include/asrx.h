@@ -210,7 +210,9 @@ int asrx_attn_fwd(int prec, const float* q, const int64_t* sq, const float* k, c
                   int64_t Lk, int64_t hd, int causal, float scale, asrx_stream_t stream);
 /* asrx_attn_fwd / _bwd with storage types (prec 1 only when io != 0): io bit 0 = q / k / v stored bf16
  * (what the per-head AbbyNormal and the v projection write when attention is their only consumer),
- * bit 1 = o stored bf16 (it only feeds the out projection, model.py:316-317), bit 2 = dO stored bf16. */
+ * bit 1 = o stored bf16 (it only feeds the out projection, model.py:316-317), bit 2 = dO stored bf16.
+ * Strides are multiples of 4 elements; those of a bf16-stored q / k / v / dO multiples of 8 (16-byte loads).
+ * Every argument check answers before anything is launched. */
 int asrx_attn_fwd2(int prec, int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk,
                    const void* v, const int64_t* sv, void* o, const int64_t* so, float* lse, int64_t B, int64_t H,
                    int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale, asrx_stream_t stream);
