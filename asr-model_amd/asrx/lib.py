@@ -64,6 +64,8 @@ SIGNATURES = {
     "asrx_rotary_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
     "asrx_rotary_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p]),
     "asrx_abby_bwd2": (_i32, [_p] * 10 + [_i64, _i64, _i32, _p]),
+    "asrx_abby64_fwd": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _i32, _p, _p, _p, _i64, _i64, _i64, _i64, _u32, _i32, _p]),
+    "asrx_abby64_bwd": (_i32, [_p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p, _i64, _i32, _p]),
     "asrx_rownorm_bwd2": (_i32, [_p, _p, _p, _p, _i64, _i64, _i32, _p]),
     "asrx_colsum_ld": (_i32, [_p, _i64, _p, _i64, _i64, _p]),
     "asrx_ce_fwd1": (_i32, [_p] * 6 + [_i64, _i64, _p]),

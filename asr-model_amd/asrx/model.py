@@ -586,8 +586,8 @@ class processor(nn.Module):  # noqa: N801  (model.py:585-629)
     def _dead_signature(self, live, x, A_in, groups, B):
         from . import msheath
         return (live, tuple(x.shape), x.dtype, tuple((tuple(a.shape), a.dtype) for a in A_in), tuple(groups), B,
-                str(x.device), prec.state(), self.training, ops.ROT_FUSED, ops.DIRECT, MSheath.fused,
-                msheath.DETERMINISTIC, gemm_mod._nj_override, gemm_mod.plan_token())
+                str(x.device), prec.state(), self.training, ops.ROT_FUSED, ops.DIRECT, ops.ABBY64_FUSED,
+                MSheath.fused, msheath.DETERMINISTIC, gemm_mod._nj_override, gemm_mod.plan_token())
 
     def _replay_dead(self, live, x, A_in, noise, B, main, s_audio, s_text):
         """Blocks 0..L-2 from the signature's HIP graphs (see graph_dead_blocks).  False: run them eagerly

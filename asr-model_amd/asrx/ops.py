@@ -561,6 +561,16 @@ def small_linear(x, W, b=None, act="none"):
 # this many rows it runs on too few workgroups (64 at the text side's 8192 rows, 40-48 us per launch), and
 # the plain GEMM (128 x 128 tiles, 3x the workgroups) + the row kernel's own SiLU / Linear(d, 3) is faster
 ROUTER_FUSED_MIN_ROWS = 32768
+# d = 64 (the per-head norms on q and k) in perf mode: router + row kernel in one pass over x (asrx_abby64_fwd)
+# and the row backward with its input-gradient product (asrx_abby64_bwd); every stored result but the
+# arrival order of the dW2 / db2 sums is bit-identical to the split path.  ASRX_ABBY64_FUSED=0: the split path.
+ABBY64_FUSED = __import__("os").environ.get("ASRX_ABBY64_FUSED", "1") != "0"
+
+
+def _abby64_fused(x, rows, res, tw, side):
+    return (ABBY64_FUSED and x.shape[-1] == 64 and prec.get() == prec.PREC_BF16 and G.use_wide(64) and x.is_cuda
+            and x.dtype == torch.float32 and rows >= ROUTER_FUSED_MIN_ROWS and res is None and tw is None
+            and not (side is not None and side.get("want_norm")) and not decisions.active())
 
 
 class AbbyNormalFn(torch.autograd.Function):
@@ -589,7 +599,16 @@ class AbbyNormalFn(torch.autograd.Function):
         if decisions.active():  # record mode 2's per-feature max-vs-avg choices of this call
             cond = torch.zeros(rows, d, dtype=torch.uint8, device=x.device)
             lib.call("asrx_abby_record_cond", _P(cond))
-        if res is not None:  # out = res + AbbyNormal(x): the residual add in the same row pass
+        ctx.fused64 = _abby64_fused(x, rows, res, tw, side)
+        if ctx.fused64:
+            Wb = G.weight_bf16(W1)
+            hpre = _E(rows, d, device=x.device) if keep else None
+            lib.require_gpu(x, Wb, out)
+            e0 = probe.begin("gemm")
+            lib.call("asrx_abby64_fwd", _P(x), _P(Wb), Wb.stride(0), _P(b1), _P(W2), _P(b2), _P(out), ob, _P(ys),
+                     _P(idx), _P(hpre), rows, L, H, sid_base, key & 0xFFFFFFFF, int(use_noise), _S())
+            probe.end("gemm", e0, 2.0 * rows * d * d, ("abby64", rows, keep, ob))
+        elif res is not None:  # out = res + AbbyNormal(x): the residual add in the same row pass
             res = _c(res)
             if G.use_wide(d) and d <= 384 and rows >= ROUTER_FUSED_MIN_ROWS:
                 hpre, logits = G.router_fwd(x.view(rows, d), W1, b1, W2, keep)
@@ -638,9 +657,14 @@ class AbbyNormalFn(torch.autograd.Function):
             dx, acc = _E(x.shape, device=x.device), 0
         dh = _E(x.shape, device=x.device)
         dW2, db2 = _gbuf(W2, fW2), _gbuf(b2, fb2)
-        lib.call("asrx_abby_bwd2", _P(gout), _P(x), _P(hpre), _P(W2), _P(ys), _P(idx), _P(dx), _P(dh), _P(dW2),
-                 _P(db2), rows, d, acc, _S())
-        G.linear_dgrad(dh, W1, out=dx, beta=1.0)
+        if ctx.fused64 and G.use_wide(d):
+            Wt = G.weight_bf16(W1, trans=True)
+            lib.call("asrx_abby64_bwd", _P(gout), _P(x), _P(hpre), _P(Wt), Wt.stride(0), _P(W2), _P(ys), _P(idx),
+                     _P(dx), _P(dh), _P(dW2), _P(db2), rows, acc, _S())
+        else:
+            lib.call("asrx_abby_bwd2", _P(gout), _P(x), _P(hpre), _P(W2), _P(ys), _P(idx), _P(dx), _P(dh), _P(dW2),
+                     _P(db2), rows, d, acc, _S())
+            G.linear_dgrad(dh, W1, out=dx, beta=1.0)
         if ctx.sink is not None:
             dx = None
         db1 = _gbuf(b1, fb1)  # bias gradient summed in the weight-gradient pass

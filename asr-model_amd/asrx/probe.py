@@ -97,7 +97,8 @@ def gemm_wr_bytes(tag):
     logits, logits-free head, router, activation-gradient) from its probe tag; None for the other GEMM kernels.  Counted once
     each: A (4 B fp32 or 2 B bf16-stored per element; a k3 conv's implicit im2col reads each activation row
     once, so K/3 of it), the bf16 weight (2 N K), C written (4 / 2 B), C or the residual read again
-    (beta / RES), the saved fp32 pre-activation; router: logits 3 x 4 B per row (+ h_pre when kept);
+    (beta / RES), the saved fp32 pre-activation; router: logits 3 x 4 B per row (+ h_pre when kept); abby64 (the
+    fused d = 64 AbbyNormal forward, which holds that router): every byte of the launch, 400 B per row with a bf16 out, 528 with fp32, + 256 with h_pre;
     activation-gradient: G read (4 B) and gz written (2 B) per output element."""
     kind = tag[0] if tag else None
     if kind == "wn":
@@ -111,6 +112,9 @@ def gemm_wr_bytes(tag):
     if kind == "router":
         _, M, N, K, keep_hpre = tag
         return 4 * M * K + 2 * N * K + 12 * M + 4 * M * N * int(keep_hpre)
+    if kind == "abby64":  # router + row kernel at d = 64 in one launch: x read, out, ys + idx (+ h_pre) written
+        _, M, keep_hpre, out_bf16 = tag
+        return M * (256 + (128 if out_bf16 else 256) + 16 + 256 * int(keep_hpre)) + 2 * 64 * 64
     if kind == "gact":
         _, M, N, K, _nj, _act, ab = tag
         return (2 if ab else 4) * M * K + 2 * N * K + 6 * M * N

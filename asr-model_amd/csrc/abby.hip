@@ -17,6 +17,12 @@
 // Backward (same kernel family) returns dx (direct + pooling + cv paths), dh_pre (rows x d) and
 // accumulates dW2 (3 x d) / db2 (3) with one atomic per element per workgroup; the host adds
 // dh_pre @ W1 into dx and computes dW1 / db1 with the GEMM.
+//
+// d = 64 (the per-head norms on q and k) has kernels of its own: abby_fwd64 / abby_bwd64_kernel (16 lanes x
+// float4 per row, DPP only; the split path behind asrx_gemm_wn_router), and in perf mode abby64_fwd_kernel --
+// router64_kernel's MFMA router and the row arithmetic in one pass over x, logits never stored -- and
+// abby64_bwd_kernel -- the row backward with dx += dh_pre @ W1 on the MFMA, dx stored once.  Both are
+// bit-identical to the kernels they replace (see the comment above them).
 #include "common.h"
 
 namespace asrx {
@@ -992,6 +998,419 @@ __global__ __launch_bounds__(64 * ABBY_WAVES) void abby_bwd64_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// d = 64, perf mode: the router and the row kernel in one pass over x (abby64_fwd_kernel), and the row
+// backward with the input-gradient product dh W1 (abby64_bwd_kernel).  A wave owns 16-row groups.  The
+// MFMA side is router64_kernel's (gemm_wn.hip): the 64 x 64 bf16 weight stays in 32 registers as the row
+// operand, a group is 8 v_mfma_f32_16x16x32_bf16 (k-blocks 0, 1 in order), lane (lr = l & 15, lk = l >> 4)
+// holds row lr / k 8 lk .. + 7 of each k-half on the way in and row lr / columns 16 nb + 4 lk .. + 3 on the
+// way out.  The row side is abby_fwd64 / abby_bwd64's (16 lanes x float4 per row, 4 rows per wave pass, 4
+// passes per group).  The two layouts meet in a per-wave LDS tile with rows of A64_LD floats (272 B: the 16
+// rows of one float4 column land in 16 different bank quads).
+//
+// Roundings: gemm_wn.o is compiled with the default contraction (its `alpha * acc + bias` and `s += h * w2`
+// are fused multiply-adds; alpha = 1, so the first is the plain sum), this file with none.  The router
+// part below writes those as the sum and as fmaf and keeps every other expression and the logit sum order
+// of router64_kernel; the row parts are the code of abby_fwd64 / abby_bwd64_kernel.  So out, ys, idx and
+// h_pre are the bits of the two-kernel path (tests/test_gpu_abby64_fused.py).
+constexpr int A64_LD = 68;   // floats per tile row
+constexpr int A64_LDH = 72;  // bf16 per row of the backward's dh tile (144 B)
+
+struct A64X {
+  float4 v[4];  // lane (row l & 15): k 8 (l >> 4) .. + 7 of k-halves 0 and 1
+};
+
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+template <typename TO>
+__global__ __launch_bounds__(64 * ABBY_WAVES) void abby64_fwd_kernel(
+    const float* __restrict__ x, const unsigned short* __restrict__ W1, int64_t ldw, const float* __restrict__ b1,
+    const float* __restrict__ W2, const float* __restrict__ b2, TO* __restrict__ out, float* __restrict__ ys,
+    int* __restrict__ idx_out, float* __restrict__ hpre, AbbyGeom g) {
+  __shared__ __attribute__((aligned(16))) float xt_all[ABBY_WAVES][16 * A64_LD];
+  __shared__ __attribute__((aligned(16))) float st_all[ABBY_WAVES][16 * 2];  // (sd, mean|x|) of the group's rows
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4;  // also the row side's l16 and row-in-pass
+  float* xt = xt_all[wid];
+  float* st = st_all[wid];
+  bf16x8 wf[4][2];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+      wf[nb][kb] = *reinterpret_cast<const bf16x8*>(W1 + (int64_t)(16 * nb + lr) * ldw + 32 * kb + 8 * lk);
+  float bv[4][4], w2v[3][4][4];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int n = 16 * nb + 4 * lk + q;
+      bv[nb][q] = b1 ? b1[n] : 0.f;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) w2v[k][nb][q] = W2[k * 64 + n];
+    }
+  const float b20 = b2[0], b21 = b2[1], b22 = b2[2];
+  g.key = noise_key(g.key);
+  const int64_t ngroups = (g.rows + 15) / 16;
+  const int64_t step = (int64_t)gridDim.x * ABBY_WAVES;
+  auto fetch = [&](int64_t grp, A64X& xs) __attribute__((always_inline)) {
+    const int64_t r0 = grp * 16 + lr;
+    const int64_t row = r0 < g.rows ? r0 : g.rows - 1;  // past the end: a valid row, results dropped
+    const float* src = x + row * 64 + 8 * lk;
+    xs.v[0] = *reinterpret_cast<const float4*>(src);
+    xs.v[1] = *reinterpret_cast<const float4*>(src + 4);
+    xs.v[2] = *reinterpret_cast<const float4*>(src + 32);
+    xs.v[3] = *reinterpret_cast<const float4*>(src + 36);
+  };
+  auto group = [&](int64_t grp, const A64X& xs) __attribute__((always_inline)) {
+    // ---- router (router64_kernel's group)
+    bf16x8 xf[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      const float4 a = xs.v[2 * kb], b = xs.v[2 * kb + 1];
+      xf[kb] = bf16x8{(__bf16)a.x, (__bf16)a.y, (__bf16)a.z, (__bf16)a.w,
+                      (__bf16)b.x, (__bf16)b.y, (__bf16)b.z, (__bf16)b.w};
+    }
+    // the group's fp32 rows for the row side
+    *reinterpret_cast<float4*>(xt + lr * A64_LD + 8 * lk) = xs.v[0];
+    *reinterpret_cast<float4*>(xt + lr * A64_LD + 8 * lk + 4) = xs.v[1];
+    *reinterpret_cast<float4*>(xt + lr * A64_LD + 8 * lk + 32) = xs.v[2];
+    *reinterpret_cast<float4*>(xt + lr * A64_LD + 8 * lk + 36) = xs.v[3];
+    f32x4 acc[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nb][kb], xf[kb], acc[nb], 0, 0, 0);
+    const int64_t mrow = grp * 16 + lr;
+    float s[2][3];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int nb = 2 * half + nt;
+        // 1 * acc + bias as one rounding
+        const float v[4] = {acc[nb][0] + bv[nb][0], acc[nb][1] + bv[nb][1], acc[nb][2] + bv[nb][2],
+                            acc[nb][3] + bv[nb][3]};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float h = silu_f(v[q]);
+          s0 = fmaf(h, w2v[0][nb][q], s0);
+          s1 = fmaf(h, w2v[1][nb][q], s1);
+          s2 = fmaf(h, w2v[2][nb][q], s2);
+        }
+        if (hpre && mrow < g.rows)
+          *reinterpret_cast<float4*>(hpre + mrow * 64 + 16 * nb + 4 * lk) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+      s0 += __shfl_xor(s0, 16); s1 += __shfl_xor(s1, 16); s2 += __shfl_xor(s2, 16);
+      s0 += __shfl_xor(s0, 32); s1 += __shfl_xor(s1, 32); s2 += __shfl_xor(s2, 32);
+      s[half][0] = s0; s[half][1] = s1; s[half][2] = s2;
+    }
+    float lz[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lz[k] = s[0][k] + s[1][k] + 0.f + 0.f;  // row lr's logits, in every lane of it
+    wave_lds_sync();
+    // ---- rows (abby_fwd64_kernel's arithmetic).  Pass `it` takes rows 4 it .. + 3 of the group, 16 lanes x float4
+    // each; rows past the end compute on the clamped row's values and store nothing.  The reductions keep their
+    // 16-lane DPP order; what follows them per ROW (cv, gumbel, softmax, mode) is the same IEEE expression whichever
+    // lane evaluates it, so it runs once per group with lane (lr, lk) on row lr instead of in all 16 lanes of each
+    // of the four passes (every lane of a row holds the same sums: each DPP step adds a pair both ways).
+    const int l16 = lr;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int rr = 4 * it + lk;
+      const Row64 xr = ld64(xt + rr * A64_LD + 4 * l16);
+      float mu, sd, mabs;
+      stats64(xr.v, mu, sd, mabs);
+      if (l16 == 0) *reinterpret_cast<float2*>(st + 2 * rr) = make_float2(sd, mabs);
+    }
+    wave_lds_sync();
+    int sel;
+    {
+      const float2 sm = *reinterpret_cast<const float2*>(st + 2 * lr);
+      const float cv = sm.x / (sm.y + 1e-6f);
+      float z0 = lz[0] + b20 + cv, z1 = lz[1] + b21 + cv, z2 = lz[2] + b22 + cv;
+      if (g.use_noise) {  // lane (lr, k) draws row lr's gumbel k
+        const float gk = noise_gumbel_k(g.key, abby_noise_idx(g, mrow, lk < 3 ? lk : 0));
+        z0 += __shfl(gk, lr);
+        z1 += __shfl(gk, lr + 16);
+        z2 += __shfl(gk, lr + 32);
+      }
+      const float zm = fmaxf(z0, fmaxf(z1, z2));
+      const float e0 = expf(z0 - zm), e1 = expf(z1 - zm), e2 = expf(z2 - zm);
+      const float inv = 1.0f / (e0 + e1 + e2);
+      const float y0 = e0 * inv, y1 = e1 * inv, y2 = e2 * inv;
+      sel = 0;
+      float ym = y0;
+      if (y1 > ym) {
+        sel = 1;
+        ym = y1;
+      }
+      if (y2 > ym) sel = 2;
+      if (lk == 0 && mrow < g.rows) {
+        ys[mrow * 3 + 0] = y0;
+        ys[mrow * 3 + 1] = y1;
+        ys[mrow * 3 + 2] = y2;
+        idx_out[mrow] = sel;
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      const int rr = 4 * it + lk;
+      const int64_t r = grp * 16 + rr;
+      const int rsel = __shfl(sel, rr);  // lane rr is (lr = rr, lk = 0)
+      const Row64 xr = ld64(xt + rr * A64_LD + 4 * l16);
+      const float(&xv)[4] = xr.v;
+      float sq[4] = {xv[0] * xv[0], xv[1] * xv[1], xv[2] * xv[2], xv[3] * xv[3]};
+      float h[6];
+      halo64(sq, h);
+      float ov[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float avg = (fmaxf(h[e], 0.f) + h[e + 1] + fmaxf(h[e + 2], 0.f)) * (1.0f / 3.0f);
+        const float mx = fmaxf(h[e], fmaxf(h[e + 1], h[e + 2]));
+        const float div = (rsel == 1 && mx > 2.0f * avg) ? mx : avg;
+        float base;
+        ov[e] = xv[e] * abby_idenom(div, base);
+      }
+      if (r < g.rows) st64(out + r * 64 + 4 * l16, ov);
+    }
+    wave_lds_sync();  // the next group overwrites the tile
+  };
+  int64_t grp = (int64_t)blockIdx.x * ABBY_WAVES + wid;
+  if (grp >= ngroups) return;
+  // the next TWO groups' x are in flight while a group is computed (two named register sets, see abby_fwd_kernel)
+  A64X xa, xb;
+  fetch(grp, xa);
+  fetch(grp + step, xb);
+  for (;; grp += 2 * step) {
+    {
+      const A64X xs = xa;
+      fetch(grp + 2 * step, xa);
+      group(grp, xs);
+    }
+    if (grp + step >= ngroups) break;
+    {
+      const A64X xs = xb;
+      fetch(grp + 3 * step, xb);
+      group(grp + step, xs);
+    }
+    if (grp + 2 * step >= ngroups) break;
+  }
+}
+
+struct B64In {  // one pass's operands of abby64_bwd_kernel
+  Row64 x, g, h, o;
+  int sel;
+  float y[3];
+};
+
+// Backward: the rows of abby_bwd64_kernel (dx direct [+ old], dh, dW2 / db2 partials), then dh rounded to bf16
+// (the GEMM's load rounding) times W1 on the MFMA with W1^T (weight_bf16(W1, trans=True): 64 in x 64 out) in
+// registers, and ONE store of dx = (direct [+ old]) + dh W1 -- the sum the beta = 1 GEMM epilogue forms
+// (1 * acc + 0, then + 1 * dx), so dx is bit-identical to asrx_abby_bwd2 + linear_dgrad.  dh is still written
+// (fp32) for the weight gradient.
+// (176 VGPRs + 16 AGPRs, two waves per SIMD; asking the allocator for three or four spills 8 / 43 registers)
+__global__ __launch_bounds__(64 * ABBY_WAVES) void abby64_bwd_kernel(
+    const float* __restrict__ dout, const float* __restrict__ x, const float* __restrict__ hpre,
+    const unsigned short* __restrict__ W1t, int64_t ldw, const float* __restrict__ W2, const float* __restrict__ ys,
+    const int* __restrict__ idx_in, float* __restrict__ dx, float* __restrict__ dhpre, float* __restrict__ dW2,
+    float* __restrict__ db2, AbbyGeom g) {
+  __shared__ __attribute__((aligned(16))) unsigned short dht_all[ABBY_WAVES][16 * A64_LDH];
+  __shared__ __attribute__((aligned(16))) float dxt_all[ABBY_WAVES][16 * A64_LD];
+  static_assert(ABBY_WAVES * 4 * (3 * 64 + 3) <= ABBY_WAVES * 16 * A64_LD, "the dW2 / db2 staging reuses the dx tiles");
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int lr = lane & 15, lk = lane >> 4, l16 = lr;
+  unsigned short* dht = dht_all[wid];
+  float* dxt = dxt_all[wid];
+  bf16x8 wf[4][2];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+      wf[nb][kb] = *reinterpret_cast<const bf16x8*>(W1t + (int64_t)(16 * nb + lr) * ldw + 32 * kb + 8 * lk);
+  float accW[3][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  float accb[3] = {0.f, 0.f, 0.f};
+  float w2v[3][4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const Row64 t = ld64(W2 + k * 64 + 4 * l16);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w2v[k][e] = t.v[e];
+  }
+  const int64_t ngroups = (g.rows + 15) / 16;
+  const int64_t step = (int64_t)gridDim.x * ABBY_WAVES;
+  auto fetch = [&](int64_t grp, int it, B64In& d) __attribute__((always_inline)) {
+    const int64_t r0 = grp * 16 + 4 * it + lk;
+    const int64_t r = r0 < g.rows ? r0 : g.rows - 1;  // past the end: a valid row, results dropped
+    d.x = ld64(x + r * 64 + 4 * l16);
+    d.g = ld64(dout + r * 64 + 4 * l16);
+    d.h = ld64(hpre + r * 64 + 4 * l16);
+    if (g.acc) d.o = ld64(dx + r * 64 + 4 * l16);
+    d.sel = idx_in[r];
+    d.y[0] = ys[r * 3 + 0];
+    d.y[1] = ys[r * 3 + 1];
+    d.y[2] = ys[r * 3 + 2];
+  };
+  for (int64_t grp = (int64_t)blockIdx.x * ABBY_WAVES + wid; grp < ngroups; grp += step) {
+    // the next pass's operands are in flight while a pass is computed (the loop stays rolled: unrolled, the
+    // four passes' operands and partial results took every register and left one wave per SIMD)
+    B64In nx;
+    fetch(grp, 0, nx);
+#pragma unroll 1
+    for (int it = 0; it < 4; ++it) {
+      const B64In cur = nx;
+      if (it < 3) fetch(grp, it + 1, nx);
+      const int rr = 4 * it + lk;
+      const int64_t r = grp * 16 + rr;
+      const bool live = r < g.rows;
+      const float(&xv)[4] = cur.x.v;
+      const float(&gv)[4] = cur.g.v;
+      const int sel = cur.sel;
+      const float y0 = cur.y[0], y1 = cur.y[1], y2 = cur.y[2];
+      float sq[4] = {xv[0] * xv[0], xv[1] * xv[1], xv[2] * xv[2], xv[3] * xv[3]};
+      float h[6];
+      halo64(sq, h);
+      float dxv[4], qa[4], qm[4];
+      int am[4];
+      float dd0 = 0.f, dd1 = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float avg = (fmaxf(h[e], 0.f) + h[e + 1] + fmaxf(h[e + 2], 0.f)) * (1.0f / 3.0f);
+        // max and first argmax over features 4l+e-1 .. 4l+e+1
+        float mx = h[e];
+        int a = 4 * l16 + e - 1;
+        if (h[e + 1] > mx) { mx = h[e + 1]; a = 4 * l16 + e; }
+        if (h[e + 2] > mx) { mx = h[e + 2]; a = 4 * l16 + e + 1; }
+        am[e] = a;
+        const bool cnd = mx > 2.0f * avg;
+        const float m2 = cnd ? mx : avg;
+        const float div = sel == 1 ? m2 : avg;
+        float base;
+        const float idn = abby_idenom(div, base);  // base: log2 of the denominator's base here
+        dxv[e] = gv[e] * idn;
+        const float q = -gv[e] * xv[e] * (1e-4f * 0.75f) * __builtin_amdgcn_exp2f(-1.75f * base);
+        dd0 += q * avg;
+        dd1 += q * m2;
+        const bool maxsel = sel == 1 && cnd;
+        qa[e] = maxsel ? 0.f : q * (1.0f / 3.0f);
+        qm[e] = maxsel ? q : 0.f;
+      }
+      dd0 = row16_sum(dd0);
+      dd1 = row16_sum(dd1);
+      const float dd2 = dd0;
+      // pool backward: dsq_i = qa_{i-1} + qa_i + qa_{i+1} + sum_{j in i-1..i+1, am_j == i} qm_j
+      {
+        const float qa_p = from_prev(qa[3], 0.f), qa_n = from_next(qa[0], 0.f);
+        const float qm_p = from_prev(qm[3], 0.f), qm_n = from_next(qm[0], 0.f);
+        const int am_p = from_prev_i(am[3], -2), am_n = from_next_i(am[0], -2);
+        const float qa6[6] = {qa_p, qa[0], qa[1], qa[2], qa[3], qa_n};
+        const float qm6[6] = {qm_p, qm[0], qm[1], qm[2], qm[3], qm_n};
+        const int am6[6] = {am_p, am[0], am[1], am[2], am[3], am_n};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int fi = 4 * l16 + e;
+          float s = qa6[e] + qa6[e + 1] + qa6[e + 2];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) s += am6[e + i] == fi ? qm6[e + i] : 0.f;
+          dxv[e] += 2.0f * xv[e] * s;
+        }
+      }
+      const float dot = y0 * dd0 + y1 * dd1 + y2 * dd2;
+      const float dz0 = y0 * (dd0 - dot), dz1 = y1 * (dd1 - dot), dz2 = y2 * (dd2 - dot);
+      const float dcv = dz0 + dz1 + dz2;
+      float mu, sd, mabs;
+      stats64(xv, mu, sd, mabs);
+      const float den = mabs + 1e-6f;
+      const float dsd = dcv / den;
+      const float dmabs = -dcv * sd / (den * den);
+      const float csd = sd > 0.f ? dsd / (63.f * sd) : 0.f;
+      const float cma = dmabs * (1.0f / 64.f);
+      float dh[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float sgn = xv[e] > 0.f ? 1.f : (xv[e] < 0.f ? -1.f : 0.f);
+        dxv[e] += csd * (xv[e] - mu) + cma * sgn;
+        const float hv = cur.h.v[e];
+        dh[e] = silu_grad(hv) * (dz0 * w2v[0][e] + dz1 * w2v[1][e] + dz2 * w2v[2][e]);
+        if (live) {
+          const float hs = silu_f(hv);
+          accW[0][e] += dz0 * hs;
+          accW[1][e] += dz1 * hs;
+          accW[2][e] += dz2 * hs;
+        }
+      }
+      if (g.acc) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dxv[e] += cur.o.v[e];
+      }
+      st64(dxt + rr * A64_LD + 4 * l16, dxv);  // what asrx_abby_bwd2 stores to dx
+      if (live) {
+        st64(dhpre + r * 64 + 4 * l16, dh);
+        accb[0] += dz0;
+        accb[1] += dz1;
+        accb[2] += dz2;
+      }
+      // dh as the GEMM reads it: bf16, row rr of the wave's tile
+      *reinterpret_cast<uint2*>(dht + rr * A64_LDH + 4 * l16) =
+          make_uint2(pack_bf16x2(dh[0], dh[1]), pack_bf16x2(dh[2], dh[3]));
+    }
+    wave_lds_sync();
+    // dh W1: router64_kernel's fragments with dh for x and W1^T for W1, the same two k-blocks in order
+    bf16x8 xf[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) xf[kb] = *reinterpret_cast<const bf16x8*>(dht + lr * A64_LDH + 32 * kb + 8 * lk);
+    f32x4 acc[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) acc[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nb][kb], xf[kb], acc[nb], 0, 0, 0);
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) {  // the epilogue: v = 1 * acc + 0 (no bias), then v + 1 * dx
+      float* t = dxt + lr * A64_LD + 16 * nb + 4 * lk;
+      const Row64 o = ld64(t);
+      const float v[4] = {(acc[nb][0] + 0.f) + o.v[0], (acc[nb][1] + 0.f) + o.v[1], (acc[nb][2] + 0.f) + o.v[2],
+                          (acc[nb][3] + 0.f) + o.v[3]};
+      st64(t, v);
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {  // whole 256-byte rows out
+      const int rr = 4 * it + lk;
+      const int64_t r = grp * 16 + rr;
+      const Row64 o = ld64(dxt + rr * A64_LD + 4 * l16);
+      if (r < g.rows) st64(dx + r * 64 + 4 * l16, o.v);
+    }
+    wave_lds_sync();  // the next group overwrites both tiles
+  }
+  // reduce the 16 row slots of the workgroup (4 per wave) in the dx tiles' memory, then one atomic per element
+  __syncthreads();
+  float(*wred)[3 * 64 + 3] = reinterpret_cast<float(*)[3 * 64 + 3]>(&dxt_all[0][0]);
+  const int slot = wid * 4 + lk;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wred[slot][k * 64 + 4 * l16 + e] = accW[k][e];
+  if (l16 == 0) {
+    wred[slot][192] = accb[0];
+    wred[slot][193] = accb[1];
+    wred[slot][194] = accb[2];
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < 195; j += 64 * ABBY_WAVES) {
+    float sacc = 0.f;
+    for (int q = 0; q < ABBY_WAVES * 4; ++q) sacc += wred[q][j];
+    atomicAdd(j < 192 ? dW2 + j : db2 + (j - 192), sacc);
+  }
+}
+
 }  // namespace asrx
 
 using namespace asrx;
@@ -1196,6 +1615,58 @@ extern "C" int asrx_abby_bwd(const float* dout, const float* x, const float* hpr
                              const float* ys, const int* idx, float* dx, float* dhpre, float* dW2, float* db2,
                              int64_t rows, int64_t d, hipStream_t stream) {
   return asrx_abby_bwd2(dout, x, hpre, W2, ys, idx, dx, dhpre, dW2, db2, rows, d, 0, stream);
+}
+
+static unsigned abby64_grid(int64_t rows, int64_t cap) {
+  const int64_t groups = (rows + 15) / 16;
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((groups + ABBY_WAVES - 1) / ABBY_WAVES, cap));
+}
+
+// d = 64, perf mode: asrx_gemm_wn_router (N = K = 64) + asrx_abby_fwd_logits2 in one kernel.  x (rows, 64)
+// fp32 contiguous; W1 the router's bf16 weight (64 x 64, row stride ldw); b1 (64) or NULL; W2 (3, 64); b2 (3);
+// out (rows, 64) fp32 / bf16; ys (rows, 3); idx (rows); hpre (rows, 64) or NULL (not kept).  Every output
+// is bit-identical to the two-kernel path.
+extern "C" int asrx_abby64_fwd(const float* x, const unsigned short* W1, int64_t ldw, const float* b1, const float* W2,
+                               const float* b2, void* out, int out_bf16, float* ys, int* idx, float* hpre,
+                               int64_t rows, int64_t L, int64_t H, int64_t sid_base, uint32_t key, int use_noise,
+                               hipStream_t stream) {
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(rows > 0, "asrx_abby64_fwd: rows < 0");
+  ASRX_REQUIRE(x && W1 && W2 && b2 && out && ys && idx, "asrx_abby64_fwd: x, W1, W2, b2, out, ys and idx required");
+  ASRX_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)W1 & 15) == 0 && ((uintptr_t)hpre & 15) == 0 &&
+                   ((uintptr_t)out & (out_bf16 ? 7 : 15)) == 0,
+               "asrx_abby64_fwd: x/W1/hpre 16-byte, out 16-byte (8 bf16) aligned");
+  ASRX_REQUIRE(ldw >= 64 && ldw % 8 == 0, "asrx_abby64_fwd: ldw >= 64, ldw%%8 required");
+  AbbyGeom g = make_geom(rows, 64, L, H, sid_base, key, use_noise);
+  const unsigned grid = abby64_grid(rows, 2048);  // 8 workgroups per CU on the MI355X's 256, grid-stride beyond
+  if (out_bf16)
+    abby64_fwd_kernel<unsigned short><<<grid, 64 * ABBY_WAVES, 0, stream>>>(x, W1, ldw, b1, W2, b2, (unsigned short*)out,
+                                                                          ys, idx, hpre, g);
+  else
+    abby64_fwd_kernel<float><<<grid, 64 * ABBY_WAVES, 0, stream>>>(x, W1, ldw, b1, W2, b2, (float*)out, ys, idx, hpre, g);
+  ASRX_LAUNCHED("asrx_abby64_fwd");
+}
+
+// d = 64, perf mode: asrx_abby_bwd2 + the beta = 1 input-gradient GEMM dx += dh W1 in one kernel.  W1t: the
+// bf16 copy of W1^T (64 in x 64 out, row stride ldw; weight_bf16(W1, trans=True)).  dx (acc == 0: overwritten,
+// else added to) and dh (rows, 64) fp32 are bit-identical to the two-kernel path; dW2 / db2 are accumulated.
+extern "C" int asrx_abby64_bwd(const float* dout, const float* x, const float* hpre, const unsigned short* W1t,
+                               int64_t ldw, const float* W2, const float* ys, const int* idx, float* dx, float* dh,
+                               float* dW2, float* db2, int64_t rows, int acc, hipStream_t stream) {
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(rows > 0, "asrx_abby64_bwd: rows < 0");
+  ASRX_REQUIRE(dout && x && hpre && W1t && W2 && ys && idx && dx && dh && dW2 && db2,
+               "asrx_abby64_bwd: every operand is required");
+  ASRX_REQUIRE(((uintptr_t)dout & 15) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)hpre & 15) == 0 &&
+                   ((uintptr_t)W1t & 15) == 0 && ((uintptr_t)W2 & 15) == 0 && ((uintptr_t)dx & 15) == 0 &&
+                   ((uintptr_t)dh & 15) == 0,
+               "asrx_abby64_bwd: dout/x/hpre/W1t/W2/dx/dh must be 16-byte aligned");
+  ASRX_REQUIRE(ldw >= 64 && ldw % 8 == 0, "asrx_abby64_bwd: ldw >= 64, ldw%%8 required");
+  AbbyGeom g = make_geom(rows, 64, 1, 1, 0, 0, 0);
+  g.acc = acc;
+  abby64_bwd_kernel<<<abby64_grid(rows, 1024), 64 * ABBY_WAVES, 0, stream>>>(dout, x, hpre, W1t, ldw, W2, ys, idx, dx,
+                                                                              dh, dW2, db2, g);
+  ASRX_LAUNCHED("asrx_abby64_bwd");
 }
 
 // Decision recorder for the parity tests: while buf != NULL, every AbbyNormal forward writes mode 2's

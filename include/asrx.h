@@ -199,6 +199,17 @@ int asrx_abby_bwd(const float* dout, const float* x, const float* hpre, const fl
 int asrx_abby_bwd2(const float* dout, const float* x, const float* hpre, const float* W2, const float* ys,
                    const int* idx, float* dx, float* dhpre, float* dW2, float* db2, int64_t rows, int64_t d, int acc,
                    asrx_stream_t stream);
+/* d = 64, bf16 perf mode: asrx_gemm_wn_router (N = K = 64) + asrx_abby_fwd_logits2 in one kernel, every output
+   bit-identical to the pair.  x (rows, 64) fp32 contiguous; W1 the router weight's bf16 copy (64 x 64, row stride
+   ldw); b1 (64) or NULL; hpre (rows, 64) or NULL (not kept); out fp32 or bf16. */
+int asrx_abby64_fwd(const float* x, const unsigned short* W1, int64_t ldw, const float* b1, const float* W2,
+                    const float* b2, void* out, int out_bf16, float* ys, int* idx, float* hpre, int64_t rows,
+                    int64_t L, int64_t H, int64_t sid_base, uint32_t key, int use_noise, asrx_stream_t stream);
+/* d = 64, bf16 perf mode: asrx_abby_bwd2 + the beta = 1 input-gradient GEMM (dx += dh W1) in one kernel.  W1t: the
+   bf16 copy of W1^T (64 x 64, row stride ldw).  dx and dh (fp32) are bit-identical to the pair. */
+int asrx_abby64_bwd(const float* dout, const float* x, const float* hpre, const unsigned short* W1t, int64_t ldw,
+                    const float* W2, const float* ys, const int* idx, float* dx, float* dh, float* dW2, float* db2,
+                    int64_t rows, int acc, asrx_stream_t stream);
 
 /* ---- attention: F.scaled_dot_product_attention(q,k,v,is_causal) at model.py:307, head dim hd = 64
  *      (tiny/small/medium) or 128 (the reference's Dimensions(dims=512, head=4), model.py:746).
