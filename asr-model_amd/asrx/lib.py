@@ -180,6 +180,10 @@ SIGNATURES = {
                               _p]),
     "asrx_attn_bwd2": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                               _i64, _i64, _i64, _i64, _i64, _i32, _f32, _p]),
+    "asrx_lattn_fwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32,
+                              _f32, _p]),
+    "asrx_lattn_bwd": (_i32, [_i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                              _i64, _i64, _i64, _i64, _i64, _i32, _f32, _p]),
     "asrx_small_linear_fwd2": (_i32, [_p, _i32, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
     "asrx_small_linear_bwd2": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _p]),
     "asrx_tgate_fwd2": (_i32, [_p, _p, _p, _i32, _i64, _i64, _p]),

@@ -284,10 +284,12 @@ class attention(nn.Module):  # noqa: N801
                               self.scale)
         return self.ln.run(q.view(B, L, H, hd), noise, site + ".qh", sid_base, L, H, out_bf16=prec.attn_bf16_io())
 
-    def run(self, x, kv, noise, site, sid_base, masked, residual=None):
+    def run(self, x, kv, noise, site, sid_base, masked, residual=None, lens=None):
         """x: attention input (B, Lq, D); kv: None (self attention on x) or (k, v) of the cross
         source.  Returns the out-projected (B, Lq, D), plus `residual` when given (the residual add
-        of model.py:578-580 fused into the out projection's epilogue)."""
+        of model.py:578-580 fused into the out projection's epilogue).  lens (ops.attn_lens): per-sample
+        lengths of the zero-padded batch -- the lengths of x as q and, for a cross call, those of the cross
+        source as k; no sample's live rows then depend on the pad rows."""
         B, L, D = x.shape
         x = ops.fork(x)  # read by the q (and, self-attention, kv) AbbyNormal and rotary's |x|
         if kv is None:
@@ -299,7 +301,7 @@ class attention(nn.Module):  # noqa: N801
         # cancellation into errors of several times the largest parameter gradient (tools/
         # debug_storage_grad.py).  So o is stored bf16 only without a backward (dead blocks, eval).
         o = ops.attention(q, kv[0], kv[1], masked, out_bf16=not ops._grad_needed(q, kv[0], kv[1]),
-                          merge_heads=True)
+                          merge_heads=True, lens=lens)
         if residual is not None:
             return ops.linear_residual(residual, o, self.out[1].weight, self.out[1].bias)
         return ops.linear(o, self.out[1].weight, self.out[1].bias)  # o: (B, L, D), heads merged

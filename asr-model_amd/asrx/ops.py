@@ -763,18 +763,77 @@ def _addr(arr):
     return ctypes.cast(arr, ctypes.c_void_p)
 
 
+class AttnLens:
+    """Per-sample query and key lengths of one batch (attn_lens): the host tuples `q_lens` / `k_lens` and
+    `table`, the int32 (B, 2) device table {q_len, k_len} the attention kernels read."""
+
+    __slots__ = ("q_lens", "k_lens", "table", "B")
+
+    def __init__(self, q_lens, k_lens, table):
+        self.q_lens, self.k_lens, self.table, self.B = q_lens, k_lens, table, len(q_lens)
+
+    def pairs(self) -> int:
+        """Sum over the samples of q_len * k_len: the live score entries of a non-causal call."""
+        return sum(a * b for a, b in zip(self.q_lens, self.k_lens))
+
+    def check(self, B, Lq, Lk, device) -> bool:
+        """Host check against a call's extents (ValueError); -> whether every sample is full length."""
+        if self.B != B:
+            raise ValueError(f"attention: lens holds {self.B} samples, the batch {B}")
+        if max(self.q_lens) > Lq or max(self.k_lens) > Lk:
+            raise ValueError(f"attention: lens up to ({max(self.q_lens)}, {max(self.k_lens)}) exceed the "
+                             f"sequence lengths ({Lq}, {Lk})")
+        if self.table.device != device:
+            raise ValueError(f"attention: lens table on {self.table.device}, tensors on {device}")
+        return min(self.q_lens) == Lq and min(self.k_lens) == Lk
+
+
+def _host_lens(x, what):
+    if isinstance(x, torch.Tensor):
+        if x.device.type != "cpu":
+            raise TypeError(f"attn_lens: {what} is a device tensor (reading it would synchronise): pass host integers")
+        x = x.tolist()
+    if not isinstance(x, (list, tuple)):
+        raise TypeError(f"attn_lens: {what} must be a list, a tuple or a CPU tensor of integers")
+    out = tuple(int(a) for a in x)
+    if any(a != b for a, b in zip(out, x)):
+        raise TypeError(f"attn_lens: {what} must hold integers")
+    if not out or min(out) < 1:
+        raise ValueError(f"attn_lens: {what} must hold lengths >= 1, got {list(x)}")
+    return out
+
+
+def attn_lens(q_lens, k_lens=None, device=None) -> AttnLens:
+    """Per-sample lengths for attention(..., lens=): q_lens / k_lens are host integers (a list, a tuple or a CPU
+    tensor; a device tensor raises TypeError, reading it would synchronise), k_lens=None means self-attention
+    (the keys are the queries).  The (B, 2) int32 device table is filled once through pinned memory with a
+    non-blocking copy: make one per batch, outside graph capture, and reuse it for every attention call of the
+    step (a cross call takes the text lengths as q and the audio lengths as k)."""
+    ql = _host_lens(q_lens, "q_lens")
+    kl = ql if k_lens is None else _host_lens(k_lens, "k_lens")
+    if len(kl) != len(ql):
+        raise ValueError(f"attn_lens: {len(ql)} query lengths, {len(kl)} key lengths")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    host = torch.tensor([ql, kl], dtype=torch.int32).t().contiguous().pin_memory()
+    return AttnLens(ql, kl, host.to(dev, non_blocking=True))
+
+
 class AttentionFn(torch.autograd.Function):
     """SDPA(q, k, v, is_causal) (model.py:307) on (B, L, H, hd) views; scale 1/sqrt(hd).  q / k / v are
     stored fp32 or bf16 (all the same); o is stored bf16 when out_bf16 (it only feeds the out
-    projection) -- bf16 storage needs the bf16 flash kernels."""
+    projection) -- bf16 storage needs the bf16 flash kernels.  lens (an AttnLens checked by attention()):
+    the per-sample-length entry points, forward and backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, out_bf16=False, sinks=(None, None, None), osink=None, merge=False):
+    def forward(ctx, q, k, v, causal, out_bf16=False, sinks=(None, None, None), osink=None, merge=False, lens=None):
         ctx.set_materialize_grads(False)
         ctx.sinks, ctx.osink = sinks, osink
+        ctx.lens = lens
         B, Lq, H, hd = q.shape
         Lk = k.shape[1]
         ap = prec.attention_prec()
+        if lens is not None and ap == prec.PREC_FP8ATT:
+            ap = prec.PREC_BF16  # per-sample lengths are not built for the fp8 forward: the bf16 kernels
         ib = G.is_bf16(q)
         if not (G.is_bf16(k) == ib and G.is_bf16(v) == ib) or (ib and ap != prec.PREC_BF16):
             q, k, v = q.float(), k.float(), v.float()  # mixed or non-bf16-kernel: fp32 storage
@@ -785,9 +844,15 @@ class AttentionFn(torch.autograd.Function):
         sq, sk, sv, so = _st3(q), _st3(k), _st3(v), _st3(o)
         io = int(ib) | (2 * int(ob))
         e0 = probe.begin("attn")
-        lib.call("asrx_attn_fwd2", ap, io, _P(q), _addr(sq), _P(k), _addr(sk), _P(v), _addr(sv), _P(o), _addr(so),
-                 _P(lse), B, H, Lq, Lk, hd, int(causal), 1.0 / math.sqrt(hd), _S())
-        probe.end("attn", e0, 4.0 * B * H * Lq * Lk * hd * (0.5 if causal else 1.0), ("attn", Lq, Lk, io))
+        if lens is None:
+            lib.call("asrx_attn_fwd2", ap, io, _P(q), _addr(sq), _P(k), _addr(sk), _P(v), _addr(sv), _P(o), _addr(so),
+                     _P(lse), B, H, Lq, Lk, hd, int(causal), 1.0 / math.sqrt(hd), _S())
+            pairs = B * Lq * Lk
+        else:
+            lib.call("asrx_lattn_fwd", ap, io, _P(q), _addr(sq), _P(k), _addr(sk), _P(v), _addr(sv), _P(o), _addr(so),
+                     _P(lse), _P(lens.table), B, H, Lq, Lk, hd, int(causal), 1.0 / math.sqrt(hd), _S())
+            pairs = lens.pairs()
+        probe.end("attn", e0, 4.0 * H * pairs * hd * (0.5 if causal else 1.0), ("attn", Lq, Lk, io))
         ctx.causal = causal
         ctx.prec = prec.attention_bwd_prec()
         ctx.io = io
@@ -800,7 +865,7 @@ class AttentionFn(torch.autograd.Function):
         q, k, v, o, lse = ctx.saved_tensors
         go = grad_in(go, ctx.osink)
         if go is None:
-            return None, None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None, None
         B, Lq, H, hd = q.shape
         go = go.view(B, Lq, H, hd)
         Lk = k.shape[1]
@@ -824,25 +889,40 @@ class AttentionFn(torch.autograd.Function):
         delta = _E(B, H, Lq, device=q.device)
         io = ctx.io | (4 * int(G.is_bf16(go)))
         arrs = [_st3(t) for t in (q, k, v, o, go, dq, dk, dv)]
-        lib.call("asrx_attn_bwd2", ctx.prec, io, _P(q), _addr(arrs[0]), _P(k), _addr(arrs[1]), _P(v), _addr(arrs[2]),
-                 _P(o), _addr(arrs[3]), _P(go), _addr(arrs[4]), _P(lse), _P(delta), _P(dq), _addr(arrs[5]), _P(dk),
-                 _addr(arrs[6]), _P(dv), _addr(arrs[7]), B, H, Lq, Lk, hd, int(ctx.causal), 1.0 / math.sqrt(hd),
-                 _S())
+        if ctx.lens is None:
+            lib.call("asrx_attn_bwd2", ctx.prec, io, _P(q), _addr(arrs[0]), _P(k), _addr(arrs[1]), _P(v),
+                     _addr(arrs[2]), _P(o), _addr(arrs[3]), _P(go), _addr(arrs[4]), _P(lse), _P(delta), _P(dq),
+                     _addr(arrs[5]), _P(dk), _addr(arrs[6]), _P(dv), _addr(arrs[7]), B, H, Lq, Lk, hd, int(ctx.causal),
+                     1.0 / math.sqrt(hd), _S())
+        else:
+            lib.call("asrx_lattn_bwd", ctx.prec, io, _P(q), _addr(arrs[0]), _P(k), _addr(arrs[1]), _P(v),
+                     _addr(arrs[2]), _P(o), _addr(arrs[3]), _P(go), _addr(arrs[4]), _P(lse), _P(delta), _P(dq),
+                     _addr(arrs[5]), _P(dk), _addr(arrs[6]), _P(dv), _addr(arrs[7]), _P(ctx.lens.table), B, H, Lq, Lk,
+                     hd, int(ctx.causal), 1.0 / math.sqrt(hd), _S())
         res = []
         for g, buf, sk in zip((dq, dk, dv), adds, ctx.sinks):
             if buf is not None:
                 lib.call("asrx_lincomb", _P(buf), _P(g), None, 1.0, 1.0, 0.0, _P(buf), buf.numel(), _S())
             res.append(None if sk is not None else g)
-        return res[0], res[1], res[2], None, None, None, None, None
+        return res[0], res[1], res[2], None, None, None, None, None, None
 
 
-def attention(q, k, v, causal, out_bf16=False, merge_heads=False):
+def attention(q, k, v, causal, out_bf16=False, merge_heads=False, lens=None):
     """SDPA (model.py:307) on (B, L, H, hd) -> (B, Lq, H, hd), or (B, Lq, H * hd) with merge_heads;
-    out_bf16: the output only feeds the out projection (stored bf16 in perf mode)."""
+    out_bf16: the output only feeds the out projection (stored bf16 in perf mode).
+
+    lens (attn_lens): per-sample lengths.  Sample b's query rows [0, q_lens[b]) attend to its keys
+    [0, k_lens[b]) exactly as that sample alone, unpadded, would; output rows past q_lens[b] are zero, the
+    gradients of q rows past q_lens[b] and of k / v rows past k_lens[b] are zero, and nothing live depends on
+    what the dead rows of q / k / v or of the incoming gradient hold.  A batch whose samples are all full length
+    takes the uniform kernels (bit-identical).  In the fp8 attention mode a call with lens runs the bf16 kernels
+    forward, as the backward already does: per-sample lengths are not built for the fp8 forward."""
+    if lens is not None and lens.check(q.shape[0], q.shape[1], k.shape[1], q.device):
+        lens = None
     grad = _grad_needed(q, k, v)
     osink = new_sink(out_bf16) if grad else None
     sinks = tuple(sink_of(t) for t in (q, k, v)) if grad else (None, None, None)
-    return out_sink(AttentionFn.apply(q, k, v, causal, out_bf16, sinks, osink, merge_heads), osink)
+    return out_sink(AttentionFn.apply(q, k, v, causal, out_bf16, sinks, osink, merge_heads, lens), osink)
 
 
 # =============================================================================== rotary

@@ -80,13 +80,30 @@ __device__ __forceinline__ void dot_rows_t(f32x4 (&acc)[HD / 16], const float* T
   }
 }
 
-// ------------------------------------------------------------------------------------ forward
+// this lane's share (columns 16 n + lc of rows r0 .. r0 + 3) of the rows of Y in [lo, hi) set to zero: the
+// dead rows of the LENS kernels
 template <int HD>
+__device__ __forceinline__ void zero_rows_f32(float* yb, int64_t stride_l, int64_t r0, int64_t lo, int64_t hi, int lc) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t row = r0 + r;
+    if (row < lo || row >= hi) continue;
+#pragma unroll
+    for (int n = 0; n < HD / 16; ++n) yb[row * stride_l + n * 16 + lc] = 0.f;
+  }
+}
+
+// ------------------------------------------------------------------------------------ forward
+// LENS (all three kernels): per-sample row limits from the `lens` table (lens_pair, common.h).  A workgroup
+// with no live row stores its zeros and leaves ahead of the first load and the first barrier (the test is
+// workgroup-uniform); a dead row of a live workgroup is stored as zero.
+template <int HD, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                            const float* __restrict__ v, float* __restrict__ o,
                                                            float* __restrict__ lse, AttnStrides sq, AttnStrides sk,
                                                            AttnStrides sv, AttnStrides so, int64_t H, int64_t Lq,
-                                                           int64_t Lk, int causal, float scale) {
+                                                           int64_t Lk, int causal, float scale,
+                                                           const int32_t* __restrict__ lens = nullptr) {
   constexpr int S = F32T<HD>::S;
   __shared__ __attribute__((aligned(16))) float Ks[ATILE * S];
   __shared__ __attribute__((aligned(16))) float Vs[ATILE * S];
@@ -99,9 +116,20 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
   const float* kb = k + b * sk.b + h * sk.h;
   const float* vb = v + b * sv.b + h * sv.h;
   const int64_t qw = q0 + wid * 16;  // first query row of this wave
+  int64_t ql = Lq, kl = Lk;          // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (q0 >= ql || kl == 0) {
+      zero_rows_f32<HD>(o + b * so.b + h * so.h, so.l, qw + lr4, 0, Lq, lc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (lc == 0 && qw + lr4 + r < Lq) lse[((int64_t)b * H + h) * Lq + qw + lr4 + r] = 0.f;
+      return;
+    }
+  }
 
   float qa[HD / 4];
-  load_frag<HD>(qa, q + b * sq.b + h * sq.h, sq.l, qw + lc, Lq, lk);
+  load_frag<HD>(qa, q + b * sq.b + h * sq.h, sq.l, qw + lc, ql, lk);
 
   f32x4 acc[HD / 16];
 #pragma unroll
@@ -112,12 +140,12 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
     m[r] = -1e30f;
     l[r] = 0.f;
   }
-  int64_t kend = Lk;
-  if (causal) kend = min(Lk, q0 + ATILE);
+  int64_t kend = kl;
+  if (causal) kend = min(kl, q0 + ATILE);
   for (int64_t k0 = 0; k0 < kend; k0 += ATILE) {
     __syncthreads();
-    stage_f32<HD>(Ks, kb, sk, k0, Lk);
-    stage_f32<HD>(Vs, vb, sv, k0, Lk);
+    stage_f32<HD>(Ks, kb, sk, k0, kl);
+    stage_f32<HD>(Vs, vb, sv, k0, kl);
     __syncthreads();
     f32x4 s[4];
 #pragma unroll
@@ -135,7 +163,7 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
       for (int r = 0; r < 4; ++r) {
         const int64_t qi = qw + lr4 + r;
         float val = s[n][r] * scale;
-        if (key >= Lk || (causal && key > qi)) val = -INFINITY;
+        if (key >= kl || (causal && key > qi)) val = -INFINITY;
         s[n][r] = val;
         tmax[r] = fmaxf(tmax[r], val);
       }
@@ -182,11 +210,19 @@ __global__ __launch_bounds__(256) void attn_fwd_f32_kernel(const float* __restri
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t qi = qw + lr4 + r;
-    if (qi >= Lq) continue;
+    if (qi >= ql) continue;
     const float inv = 1.0f / l[r];
 #pragma unroll
     for (int n = 0; n < HD / 16; ++n) ob[qi * so.l + n * 16 + lc] = acc[n][r] * inv;
     if (lc == 0) lse[((int64_t)b * H + h) * Lq + qi] = m[r] + logf(l[r]);
+  }
+  if constexpr (LENS) {
+    zero_rows_f32<HD>(ob, so.l, qw + lr4, ql, Lq, lc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t qi = qw + lr4 + r;
+      if (lc == 0 && qi >= ql && qi < Lq) lse[((int64_t)b * H + h) * Lq + qi] = 0.f;
+    }
   }
 }
 
@@ -221,12 +257,13 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const TO* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------ dK / dV
-template <int HD>
+template <int HD, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ delta,
     float* __restrict__ dk, float* __restrict__ dv, AttnStrides sq, AttnStrides sk, AttnStrides sv, AttnStrides sd,
-    AttnStrides sdk, AttnStrides sdv, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale) {
+    AttnStrides sdk, AttnStrides sdv, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale,
+    const int32_t* __restrict__ lens = nullptr) {
   constexpr int S = F32T<HD>::S;
   __shared__ __attribute__((aligned(16))) float Qs[ATILE * S];
   __shared__ __attribute__((aligned(16))) float dOs[ATILE * S];
@@ -243,10 +280,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(
   const float* lb = lse + ((int64_t)b * H + h) * Lq;
   const float* db_ = delta + ((int64_t)b * H + h) * Lq;
   const int64_t kw = k0 + wid * 16;
+  int64_t ql = Lq, kl = Lk;  // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (k0 >= kl || ql == 0) {
+      zero_rows_f32<HD>(dk + b * sdk.b + h * sdk.h, sdk.l, kw + lr4, 0, Lk, lc);
+      zero_rows_f32<HD>(dv + b * sdv.b + h * sdv.h, sdv.l, kw + lr4, 0, Lk, lc);
+      return;
+    }
+  }
 
   float ka[HD / 4], va[HD / 4];
-  load_frag<HD>(ka, k + b * sk.b + h * sk.h, sk.l, kw + lc, Lk, lk);
-  load_frag<HD>(va, v + b * sv.b + h * sv.h, sv.l, kw + lc, Lk, lk);
+  load_frag<HD>(ka, k + b * sk.b + h * sk.h, sk.l, kw + lc, kl, lk);
+  load_frag<HD>(va, v + b * sv.b + h * sv.h, sv.l, kw + lc, kl, lk);
 
   f32x4 adk[HD / 16], adv[HD / 16];
 #pragma unroll
@@ -255,14 +301,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(
     adv[n] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int64_t qstart = causal ? (k0 / ATILE) * ATILE : 0;
-  for (int64_t q0 = qstart; q0 < Lq; q0 += ATILE) {
+  for (int64_t q0 = qstart; q0 < ql; q0 += ATILE) {
     __syncthreads();
-    stage_f32<HD>(Qs, qb, sq, q0, Lq);
-    stage_f32<HD>(dOs, gb, sd, q0, Lq);
+    stage_f32<HD>(Qs, qb, sq, q0, ql);
+    stage_f32<HD>(dOs, gb, sd, q0, ql);
     if (threadIdx.x < ATILE) {
       const int64_t qi = q0 + threadIdx.x;
-      lse_s[threadIdx.x] = qi < Lq ? lb[qi] : 0.f;
-      del_s[threadIdx.x] = qi < Lq ? db_[qi] : 0.f;
+      lse_s[threadIdx.x] = qi < ql ? lb[qi] : 0.f;
+      del_s[threadIdx.x] = qi < ql ? db_[qi] : 0.f;
     }
     __syncthreads();
     float* P = Pst[wid];
@@ -279,7 +325,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(
       for (int r = 0; r < 4; ++r) {
         const int64_t key = kw + lr4 + r;
         float p = expf(st[r] * scale - lse_s[qcol]);
-        if (qi >= Lq || key >= Lk || (causal && key > qi)) p = 0.f;
+        if (qi >= ql || key >= kl || (causal && key > qi)) p = 0.f;
         P[(lr4 + r) * PST + qcol] = p;
         D[(lr4 + r) * PST + qcol] = p * (dp[r] - del_s[qcol]);
       }
@@ -294,22 +340,26 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv_f32_kernel(
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t key = kw + lr4 + r;
-    if (key >= Lk) continue;
+    if (key >= kl) continue;
 #pragma unroll
     for (int n = 0; n < HD / 16; ++n) {
       dkb[key * sdk.l + n * 16 + lc] = adk[n][r] * scale;
       dvb[key * sdv.l + n * 16 + lc] = adv[n][r];
     }
   }
+  if constexpr (LENS) {
+    zero_rows_f32<HD>(dkb, sdk.l, kw + lr4, kl, Lk, lc);
+    zero_rows_f32<HD>(dvb, sdv.l, kw + lr4, kl, Lk, lc);
+  }
 }
 
 // ------------------------------------------------------------------------------------ dQ
-template <int HD>
+template <int HD, bool LENS = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
     const float* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ delta,
     float* __restrict__ dq, AttnStrides sq, AttnStrides sk, AttnStrides sv, AttnStrides sd, AttnStrides sdq,
-    int64_t H, int64_t Lq, int64_t Lk, int causal, float scale) {
+    int64_t H, int64_t Lq, int64_t Lk, int causal, float scale, const int32_t* __restrict__ lens = nullptr) {
   constexpr int S = F32T<HD>::S;
   __shared__ __attribute__((aligned(16))) float Ks[ATILE * S];
   __shared__ __attribute__((aligned(16))) float Vs[ATILE * S];
@@ -324,26 +374,34 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(
   const float* lb = lse + ((int64_t)b * H + h) * Lq;
   const float* db_ = delta + ((int64_t)b * H + h) * Lq;
   const int64_t qw = q0 + wid * 16;
+  int64_t ql = Lq, kl = Lk;  // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (q0 >= ql || kl == 0) {
+      zero_rows_f32<HD>(dq + b * sdq.b + h * sdq.h, sdq.l, qw + lr4, 0, Lq, lc);
+      return;
+    }
+  }
 
   float qa[HD / 4], ga[HD / 4];
-  load_frag<HD>(qa, q + b * sq.b + h * sq.h, sq.l, qw + lc, Lq, lk);
-  load_frag<HD>(ga, dO + b * sd.b + h * sd.h, sd.l, qw + lc, Lq, lk);
+  load_frag<HD>(qa, q + b * sq.b + h * sq.h, sq.l, qw + lc, ql, lk);
+  load_frag<HD>(ga, dO + b * sd.b + h * sd.h, sd.l, qw + lc, ql, lk);
   float lsev[4], delv[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t qi = qw + lr4 + r;
-    lsev[r] = qi < Lq ? lb[qi] : 0.f;
-    delv[r] = qi < Lq ? db_[qi] : 0.f;
+    lsev[r] = qi < ql ? lb[qi] : 0.f;
+    delv[r] = qi < ql ? db_[qi] : 0.f;
   }
   f32x4 adq[HD / 16];
 #pragma unroll
   for (int n = 0; n < HD / 16; ++n) adq[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  int64_t kend = Lk;
-  if (causal) kend = min(Lk, q0 + ATILE);
+  int64_t kend = kl;
+  if (causal) kend = min(kl, q0 + ATILE);
   for (int64_t k0 = 0; k0 < kend; k0 += ATILE) {
     __syncthreads();
-    stage_f32<HD>(Ks, kb, sk, k0, Lk);
-    stage_f32<HD>(Vs, vb, sv, k0, Lk);
+    stage_f32<HD>(Ks, kb, sk, k0, kl);
+    stage_f32<HD>(Vs, vb, sv, k0, kl);
     __syncthreads();
     float* D = dSs[wid];
 #pragma unroll
@@ -357,7 +415,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(
       for (int r = 0; r < 4; ++r) {
         const int64_t qi = qw + lr4 + r;
         float p = expf(s[r] * scale - lsev[r]);
-        if (qi >= Lq || key >= Lk || (causal && key > qi)) p = 0.f;
+        if (qi >= ql || key >= kl || (causal && key > qi)) p = 0.f;
         D[(lr4 + r) * PST + n * 16 + lc] = p * (dp[r] - delv[r]);
       }
     }
@@ -370,10 +428,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_f32_kernel(
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int64_t qi = qw + lr4 + r;
-    if (qi >= Lq) continue;
+    if (qi >= ql) continue;
 #pragma unroll
     for (int n = 0; n < HD / 16; ++n) dqb[qi * sdq.l + n * 16 + lc] = adq[n][r] * scale;
   }
+  if constexpr (LENS) zero_rows_f32<HD>(dqb, sdq.l, qw + lr4, ql, Lq, lc);
 }
 
 }  // namespace asrx
@@ -401,26 +460,85 @@ int attn_fwd_f8(const float* q, const int64_t* sq, const float* k, const int64_t
 constexpr int PREC_FP8ATT = 2;  // forward only: e4m3 QK^T (attn_f8.hip)
 }
 
-template <int HD>
+template <int HD, bool LENS = false>
 static void attn_fwd_f32(const float* q, AttnStrides Sq, const float* k, AttnStrides Sk, const float* v,
                          AttnStrides Sv, float* o, AttnStrides So, float* lse, int64_t B, int64_t H, int64_t Lq,
-                         int64_t Lk, int causal, float scale, hipStream_t stream) {
+                         int64_t Lk, int causal, float scale, hipStream_t stream, const int32_t* lens = nullptr) {
   dim3 g((unsigned)((Lq + ATILE - 1) / ATILE), (unsigned)H, (unsigned)B);
-  attn_fwd_f32_kernel<HD><<<g, 256, 0, stream>>>(q, k, v, o, lse, Sq, Sk, Sv, So, H, Lq, Lk, causal, scale);
+  attn_fwd_f32_kernel<HD, LENS><<<g, 256, 0, stream>>>(q, k, v, o, lse, Sq, Sk, Sv, So, H, Lq, Lk, causal, scale,
+                                                       lens);
 }
 
-template <int HD>
+template <int HD, bool LENS = false>
 static void attn_bwd_f32(const float* q, AttnStrides Sq, const float* k, AttnStrides Sk, const float* v,
                          AttnStrides Sv, const float* dO, AttnStrides Sd, const float* lse, const float* delta,
                          float* dq, AttnStrides Sdq, float* dk, AttnStrides Sdk, float* dv, AttnStrides Sdv,
-                         int64_t B, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale, hipStream_t stream) {
+                         int64_t B, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale, hipStream_t stream,
+                         const int32_t* lens = nullptr) {
   dim3 gk((unsigned)((Lk + ATILE - 1) / ATILE), (unsigned)H, (unsigned)B);
   dim3 gq((unsigned)((Lq + ATILE - 1) / ATILE), (unsigned)H, (unsigned)B);
-  attn_bwd_dkdv_f32_kernel<HD><<<gk, 256, 0, stream>>>(q, k, v, dO, lse, delta, dk, dv, Sq, Sk, Sv, Sd, Sdk, Sdv, H, Lq,
-                                                       Lk, causal, scale);
-  attn_bwd_dq_f32_kernel<HD><<<gq, 256, 0, stream>>>(q, k, v, dO, lse, delta, dq, Sq, Sk, Sv, Sd, Sdq, H, Lq, Lk,
-                                                     causal, scale);
+  attn_bwd_dkdv_f32_kernel<HD, LENS><<<gk, 256, 0, stream>>>(q, k, v, dO, lse, delta, dk, dv, Sq, Sk, Sv, Sd, Sdk, Sdv,
+                                                             H, Lq, Lk, causal, scale, lens);
+  attn_bwd_dq_f32_kernel<HD, LENS><<<gq, 256, 0, stream>>>(q, k, v, dO, lse, delta, dq, Sq, Sk, Sv, Sd, Sdq, H, Lq, Lk,
+                                                           causal, scale, lens);
 }
+
+// The Delta pass of a backward: delta_ws[b, h, i] = rowsum(dO * o) over every row of the launch extents.  io bit 1:
+// o stored bf16, bit 2: dO stored bf16; in the bf16 mode an fp32 dO is rounded as the dP MFMA sees it.
+namespace asrx {
+void attn_delta(int prec, int io, const void* o_, const int64_t* so, const void* dO_, const int64_t* sd,
+                float* delta_ws, int64_t B, int64_t H, int64_t Lq, int64_t hd, hipStream_t stream) {
+  AttnStrides So{so[0], so[1], so[2]}, Sd{sd[0], sd[1], sd[2]};
+  const int64_t rows = B * H * Lq;
+  const unsigned gd = (unsigned)std::min<int64_t>((rows + 3) / 4, 8192);
+#define ASRX_DL(HDV, TO, TD, RD) \
+  attn_delta_kernel<HDV, TO, TD, RD><<<gd, 256, 0, stream>>>((const TO*)o_, (const TD*)dO_, delta_ws, So, Sd, B, H, Lq)
+  const int dsel = ((io >> 1) & 1) | ((io >> 1) & 2);  // bit 0: o bf16, bit 1: dO bf16
+  const bool rd = prec == PREC_BF16;                  // fp32 dO rounded as the bf16 dP MFMA sees it
+  if (hd == 64) {
+    switch (dsel) {
+      case 0: if (rd) ASRX_DL(64, float, float, true); else ASRX_DL(64, float, float, false); break;
+      case 1: if (rd) ASRX_DL(64, unsigned short, float, true); else ASRX_DL(64, unsigned short, float, false); break;
+      case 2: ASRX_DL(64, float, unsigned short, false); break;
+      default: ASRX_DL(64, unsigned short, unsigned short, false); break;
+    }
+  } else {
+    switch (dsel) {
+      case 0: if (rd) ASRX_DL(128, float, float, true); else ASRX_DL(128, float, float, false); break;
+      case 1: if (rd) ASRX_DL(128, unsigned short, float, true); else ASRX_DL(128, unsigned short, float, false); break;
+      case 2: ASRX_DL(128, float, unsigned short, false); break;
+      default: ASRX_DL(128, unsigned short, unsigned short, false); break;
+    }
+  }
+#undef ASRX_DL
+}
+
+// the fp32 kernels with per-sample {q_len, k_len} limits (LENS instantiations), for attn_lens.hip
+void attn_fwd_f32_lens(const float* q, const int64_t* sq, const float* k, const int64_t* sk, const float* v,
+                       const int64_t* sv, float* o, const int64_t* so, float* lse, const int32_t* lens, int64_t B,
+                       int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale, hipStream_t stream) {
+  AttnStrides Sq{sq[0], sq[1], sq[2]}, Sk{sk[0], sk[1], sk[2]}, Sv{sv[0], sv[1], sv[2]}, So{so[0], so[1], so[2]};
+  if (hd == 64)
+    attn_fwd_f32<64, true>(q, Sq, k, Sk, v, Sv, o, So, lse, B, H, Lq, Lk, causal, scale, stream, lens);
+  else
+    attn_fwd_f32<128, true>(q, Sq, k, Sk, v, Sv, o, So, lse, B, H, Lq, Lk, causal, scale, stream, lens);
+}
+
+void attn_bwd_f32_lens(const float* q, const int64_t* sq, const float* k, const int64_t* sk, const float* v,
+                       const int64_t* sv, const float* dO, const int64_t* sd, const float* lse, const float* delta,
+                       float* dq, const int64_t* sdq, float* dk, const int64_t* sdk, float* dv, const int64_t* sdv,
+                       const int32_t* lens, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal,
+                       float scale, hipStream_t stream) {
+  AttnStrides Sq{sq[0], sq[1], sq[2]}, Sk{sk[0], sk[1], sk[2]}, Sv{sv[0], sv[1], sv[2]}, Sd{sd[0], sd[1], sd[2]};
+  AttnStrides Sdq{sdq[0], sdq[1], sdq[2]}, Sdk{sdk[0], sdk[1], sdk[2]}, Sdv{sdv[0], sdv[1], sdv[2]};
+  if (hd == 64)
+    attn_bwd_f32<64, true>(q, Sq, k, Sk, v, Sv, dO, Sd, lse, delta, dq, Sdq, dk, Sdk, dv, Sdv, B, H, Lq, Lk, causal,
+                           scale, stream, lens);
+  else
+    attn_bwd_f32<128, true>(q, Sq, k, Sk, v, Sv, dO, Sd, lse, delta, dq, Sdq, dk, Sdk, dv, Sdv, B, H, Lq, Lk, causal,
+                            scale, stream, lens);
+}
+}  // namespace asrx
 
 extern "C" int asrx_attn_fwd2(int prec, int io, const void* q_, const int64_t* sq, const void* k_, const int64_t* sk,
                               const void* v_, const int64_t* sv, void* o_, const int64_t* so, float* lse, int64_t B,
@@ -484,28 +602,7 @@ extern "C" int asrx_attn_bwd2(int prec, int io, const void* q_, const int64_t* s
   AttnStrides Sq{sq[0], sq[1], sq[2]}, Sk{sk[0], sk[1], sk[2]}, Sv{sv[0], sv[1], sv[2]}, So{so[0], so[1], so[2]};
   AttnStrides Sd{sd[0], sd[1], sd[2]}, Sdq{sdq[0], sdq[1], sdq[2]}, Sdk{sdk[0], sdk[1], sdk[2]},
       Sdv{sdv[0], sdv[1], sdv[2]};
-  const int64_t rows = B * H * Lq;
-  const unsigned gd = (unsigned)std::min<int64_t>((rows + 3) / 4, 8192);
-#define ASRX_DL(HDV, TO, TD, RD) \
-  attn_delta_kernel<HDV, TO, TD, RD><<<gd, 256, 0, stream>>>((const TO*)o_, (const TD*)dO_, delta_ws, So, Sd, B, H, Lq)
-  const int dsel = ((io >> 1) & 1) | ((io >> 1) & 2);  // bit 0: o bf16, bit 1: dO bf16
-  const bool rd = prec == PREC_BF16;                  // fp32 dO rounded as the bf16 dP MFMA sees it
-  if (hd == 64) {
-    switch (dsel) {
-      case 0: if (rd) ASRX_DL(64, float, float, true); else ASRX_DL(64, float, float, false); break;
-      case 1: if (rd) ASRX_DL(64, unsigned short, float, true); else ASRX_DL(64, unsigned short, float, false); break;
-      case 2: ASRX_DL(64, float, unsigned short, false); break;
-      default: ASRX_DL(64, unsigned short, unsigned short, false); break;
-    }
-  } else {
-    switch (dsel) {
-      case 0: if (rd) ASRX_DL(128, float, float, true); else ASRX_DL(128, float, float, false); break;
-      case 1: if (rd) ASRX_DL(128, unsigned short, float, true); else ASRX_DL(128, unsigned short, float, false); break;
-      case 2: ASRX_DL(128, float, unsigned short, false); break;
-      default: ASRX_DL(128, unsigned short, unsigned short, false); break;
-    }
-  }
-#undef ASRX_DL
+  attn_delta(prec, io, o_, so, dO_, sd, delta_ws, B, H, Lq, hd, stream);
   if (prec == PREC_BF16)
     attn_bwd_mf(io, q, sq, k, sk, v, sv, dO, sd, lse, delta_ws, dq, sdq, dk, sdk, dv, sdv, B, H, Lq, Lk, hd, causal,
                 scale, stream);

@@ -172,6 +172,17 @@ __device__ __forceinline__ void store_rowT(T* yr, const f32x16 (&acc)[HD / 32], 
     }
 }
 
+// the lane's share of row `yr` (the columns store_rowT writes) set to zero: dead rows of the LENS kernels
+template <int HD, typename T = float>
+__device__ __forceinline__ void zero_rowT(T* yr, int hi) {
+  f32x16 z[HD / 32];
+#pragma unroll
+  for (int dd = 0; dd < HD / 32; ++dd)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[dd][r] = 0.f;
+  store_rowT<HD, T>(yr, z, 0.f, hi);
+}
+
 // logical workgroup of hardware workgroup `bid` of G: consecutive logical ids on one XCD (hardware
 // ids are dealt to the 8 XCDs round-robin), so the query blocks of one (b, h) share that XCD's L2
 // copy of their K / V rows
@@ -184,13 +195,16 @@ __device__ __forceinline__ int64_t xcd_logical(int64_t bid, int64_t G) {
 // XCD: 1-D grid remapped with xcd_logical.  PRIO: MFMA issue at raised wave priority (s_setprio),
 // so a SIMD's other wave fills the matrix-core gaps with its softmax VALU work.
 // TI: storage type of q / k / v, TO: of o (float or bf16s).
-template <int HD, int WPE = 1, bool XCD = false, bool PRIO = false, typename TI = float, typename TO = float>
+// LENS: per-sample row limits from the `lens` table (lens_pair); a workgroup with no live row stores its
+// zeros and leaves ahead of the first operand load and the first barrier (the test is workgroup-uniform).
+template <int HD, int WPE = 1, bool XCD = false, bool PRIO = false, typename TI = float, typename TO = float,
+          bool LENS = false>
 __global__ __launch_bounds__(NTHR, WPE) void attn_fwd_mf_kernel(const TI* __restrict__ q, const TI* __restrict__ k,
                                                               const TI* __restrict__ v, TO* __restrict__ o,
                                                               float* __restrict__ lse, AttnStridesMF sq,
                                                               AttnStridesMF sk, AttnStridesMF sv, AttnStridesMF so,
                                                               int64_t H, int64_t Lq, int64_t Lk, int causal,
-                                                              float scale) {
+                                                              float scale, const int32_t* __restrict__ lens = nullptr) {
   constexpr int NH = HD / 64;
   __shared__ __attribute__((aligned(16))) unsigned short Ks[2][NH * HALF];
   __shared__ __attribute__((aligned(16))) unsigned short Vs[2][NH * HALF];
@@ -214,21 +228,32 @@ __global__ __launch_bounds__(NTHR, WPE) void attn_fwd_mf_kernel(const TI* __rest
   const TI* kb = k + b * sk.b + h * sk.h;
   const TI* vb = v + b * sv.b + h * sv.h;
   const float c = scale * LOG2E;
+  int64_t ql = Lq, kl = Lk;  // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (q0 >= ql || kl == 0) {
+      if (qi < Lq) {
+        zero_rowT<HD, TO>(o + b * so.b + h * so.h + qi * so.l, hi);
+        if (hi == 0) lse[((int64_t)b * H + h) * Lq + qi] = 0.f;
+      }
+      return;
+    }
+  }
 
   // Q^T fragments (B operand): lane (q = j, hi) holds Q[q][64 hf + 16 s + 8 hi .. +7]
   bf16x8 qf[HD / 16];
-  row_frags<HD>(q + b * sq.b + h * sq.h, sq.l, qi, Lq, hi, qf);
+  row_frags<HD>(q + b * sq.b + h * sq.h, sq.l, qi, ql, hi, qf);
 
-  int64_t kend = Lk;
-  if (causal) kend = min(Lk, q0 + QB);
+  int64_t kend = kl;
+  if (causal) kend = min(kl, q0 + QB);
   const int ntiles = (int)((kend + KT - 1) / KT);
   const int skey = tid >> 3, sc = tid & 7;  // staging: one 16-B chunk of each half of one key row
 
   Row8<TI> ka[NH], va[NH];
 #pragma unroll
   for (int hf = 0; hf < NH; ++hf) {
-    stage_load(kb, sk, skey, Lk, hf, sc, ka[hf]);
-    stage_load(vb, sv, skey, Lk, hf, sc, va[hf]);
+    stage_load(kb, sk, skey, kl, hf, sc, ka[hf]);
+    stage_load(vb, sv, skey, kl, hf, sc, va[hf]);
     stage_store(Ks[0] + hf * HALF, skey, sc ^ kswz(skey), ka[hf]);
     stage_store(Vs[0] + hf * HALF, skey, sc ^ vswz(skey), va[hf]);
   }
@@ -248,8 +273,8 @@ __global__ __launch_bounds__(NTHR, WPE) void attn_fwd_mf_kernel(const TI* __rest
     if (t + 1 < ntiles) {  // next tile's loads fly under this tile's MFMAs
 #pragma unroll
       for (int hf = 0; hf < NH; ++hf) {
-        stage_load(kb, sk, k0 + KT + skey, Lk, hf, sc, ka[hf]);
-        stage_load(vb, sv, k0 + KT + skey, Lk, hf, sc, va[hf]);
+        stage_load(kb, sk, k0 + KT + skey, kl, hf, sc, ka[hf]);
+        stage_load(vb, sv, k0 + KT + skey, kl, hf, sc, va[hf]);
       }
     }
     const unsigned short* Kt = Ks[buf];
@@ -270,9 +295,9 @@ __global__ __launch_bounds__(NTHR, WPE) void attn_fwd_mf_kernel(const TI* __rest
     // wave-uniform (readfirstlane: the compiler cannot prove wid uniform, and a per-lane mask flag turned the
     // block below into a 32-deep exec-masked branch chain run on EVERY tile, ~100 scalar instructions)
     const bool need_mask =
-        __builtin_amdgcn_readfirstlane((int)((k0 + KT > Lk) || (causal && k0 + KT - 1 > q0 + wid * 32))) != 0;
+        __builtin_amdgcn_readfirstlane((int)((k0 + KT > kl) || (causal && k0 + KT - 1 > q0 + wid * 32))) != 0;
     if (need_mask) {  // keys of this tile at or past lim are masked: key >= Lk, or key > qi when causal
-      const int lim = (int)min(min(Lk - k0, (int64_t)KT), causal ? qi - k0 + 1 : (int64_t)KT);
+      const int lim = (int)min(min(kl - k0, (int64_t)KT), causal ? qi - k0 + 1 : (int64_t)KT);
 #pragma unroll
       for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
@@ -354,9 +379,15 @@ __global__ __launch_bounds__(NTHR, WPE) void attn_fwd_mf_kernel(const TI* __rest
 
   // ---- finalize: l over both halves, O = O^T / l, lse in natural log
   const float lt = l + __shfl_xor(l, 32);
-  if (qi < Lq) {
+  if (qi < ql) {
     store_rowT<HD, TO>(o + b * so.b + h * so.h + qi * so.l, oacc, 1.0f / lt, hi);
     if (hi == 0) lse[((int64_t)b * H + h) * Lq + qi] = (m * c + __builtin_amdgcn_logf(lt)) * LN2;
+  }
+  if constexpr (LENS) {  // a dead row of a live workgroup: zeros, not the mean of V its zero Q fragments gave
+    if (qi >= ql && qi < Lq) {
+      zero_rowT<HD, TO>(o + b * so.b + h * so.h + qi * so.l, hi);
+      if (hi == 0) lse[((int64_t)b * H + h) * Lq + qi] = 0.f;
+    }
   }
 }
 
@@ -370,13 +401,13 @@ __global__ __launch_bounds__(NTHR, WPE) void attn_fwd_mf_kernel(const TI* __rest
 // tile is applied when its scores are made (end of the previous iteration), outside the interleaved
 // block; loads past the last tile are clamped (stage_load) and their scores never used.  Two named
 // score sets (loop unrolled by two) instead of a runtime index, which would go to scratch.
-template <bool XCD, typename TI, typename TO>
+template <bool XCD, typename TI, typename TO, bool LENS = false>
 __global__ __launch_bounds__(NTHR, 1) void attn_fwd_sp_kernel(const TI* __restrict__ q, const TI* __restrict__ k,
                                                             const TI* __restrict__ v, TO* __restrict__ o,
                                                             float* __restrict__ lse, AttnStridesMF sq,
                                                             AttnStridesMF sk, AttnStridesMF sv, AttnStridesMF so,
                                                             int64_t H, int64_t Lq, int64_t Lk, int causal,
-                                                            float scale) {
+                                                            float scale, const int32_t* __restrict__ lens = nullptr) {
   constexpr int HD = 64;
   __shared__ __attribute__((aligned(16))) unsigned short Ks[2][HALF];
   __shared__ __attribute__((aligned(16))) unsigned short Vs[2][HALF];
@@ -400,21 +431,32 @@ __global__ __launch_bounds__(NTHR, 1) void attn_fwd_sp_kernel(const TI* __restri
   const TI* kb = k + b * sk.b + h * sk.h;
   const TI* vb = v + b * sv.b + h * sv.h;
   const float c = scale * LOG2E;
+  int64_t ql = Lq, kl = Lk;  // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (q0 >= ql || kl == 0) {
+      if (qi < Lq) {
+        zero_rowT<HD, TO>(o + b * so.b + h * so.h + qi * so.l, hi);
+        if (hi == 0) lse[((int64_t)b * H + h) * Lq + qi] = 0.f;
+      }
+      return;
+    }
+  }
 
   bf16x8 qf[HD / 16];
-  row_frags<HD>(q + b * sq.b + h * sq.h, sq.l, qi, Lq, hi, qf);
+  row_frags<HD>(q + b * sq.b + h * sq.h, sq.l, qi, ql, hi, qf);
 
-  int64_t kend = Lk;
-  if (causal) kend = min(Lk, q0 + QB);
+  int64_t kend = kl;
+  if (causal) kend = min(kl, q0 + QB);
   const int ntiles = (int)((kend + KT - 1) / KT);
   const int skey = tid >> 3, sc = tid & 7;
 
   Row8<TI> ka, va;
-  stage_load(kb, sk, skey, Lk, 0, sc, ka);
-  stage_load(vb, sv, skey, Lk, 0, sc, va);
+  stage_load(kb, sk, skey, kl, 0, sc, ka);
+  stage_load(vb, sv, skey, kl, 0, sc, va);
   stage_store(Ks[0], skey, sc ^ kswz(skey), ka);
   stage_store(Vs[0], skey, sc ^ vswz(skey), va);
-  stage_load(kb, sk, KT + skey, Lk, 0, sc, ka);
+  stage_load(kb, sk, KT + skey, kl, 0, sc, ka);
   stage_store(Ks[1], skey, sc ^ kswz(skey), ka);
   __syncthreads();
 
@@ -430,9 +472,9 @@ __global__ __launch_bounds__(NTHR, 1) void attn_fwd_sp_kernel(const TI* __restri
   auto mask = [&](f32x16 (&s)[2], int tt) {
     const int64_t k0 = (int64_t)tt * KT;
     const bool need_mask =
-        __builtin_amdgcn_readfirstlane((int)((k0 + KT > Lk) || (causal && k0 + KT - 1 > q0 + wid * 32))) != 0;
+        __builtin_amdgcn_readfirstlane((int)((k0 + KT > kl) || (causal && k0 + KT - 1 > q0 + wid * 32))) != 0;
     if (need_mask) {
-      const int lim = (int)min(min(Lk - k0, (int64_t)KT), causal ? qi - k0 + 1 : (int64_t)KT);
+      const int lim = (int)min(min(kl - k0, (int64_t)KT), causal ? qi - k0 + 1 : (int64_t)KT);
 #pragma unroll
       for (int kb2 = 0; kb2 < 2; ++kb2)
 #pragma unroll
@@ -458,8 +500,8 @@ __global__ __launch_bounds__(NTHR, 1) void attn_fwd_sp_kernel(const TI* __restri
   auto step = [&](int t, f32x16 (&cur)[2], f32x16 (&nxt)[2]) {
     const int buf = t & 1;
     const int64_t k0 = (int64_t)t * KT;
-    stage_load(vb, sv, k0 + KT + skey, Lk, 0, sc, va);      // V(t + 1)
-    stage_load(kb, sk, k0 + 2 * KT + skey, Lk, 0, sc, ka);  // K(t + 2)
+    stage_load(vb, sv, k0 + KT + skey, kl, 0, sc, va);      // V(t + 1)
+    stage_load(kb, sk, k0 + 2 * KT + skey, kl, 0, sc, ka);  // K(t + 2)
 
     float tmax = -INFINITY;
 #pragma unroll
@@ -526,9 +568,15 @@ __global__ __launch_bounds__(NTHR, 1) void attn_fwd_sp_kernel(const TI* __restri
   if (t < ntiles) step(t, sA, sB);
 
   const float lt = l + __shfl_xor(l, 32);
-  if (qi < Lq) {
+  if (qi < ql) {
     store_rowT<HD, TO>(o + b * so.b + h * so.h + qi * so.l, oacc, 1.0f / lt, hi);
     if (hi == 0) lse[((int64_t)b * H + h) * Lq + qi] = (m * c + __builtin_amdgcn_logf(lt)) * LN2;
+  }
+  if constexpr (LENS) {  // a dead row of a live workgroup: zeros, not the mean of V its zero Q fragments gave
+    if (qi >= ql && qi < Lq) {
+      zero_rowT<HD, TO>(o + b * so.b + h * so.h + qi * so.l, hi);
+      if (hi == 0) lse[((int64_t)b * H + h) * Lq + qi] = 0.f;
+    }
   }
 }
 
@@ -556,13 +604,13 @@ struct BwdCfg {
 constexpr int BQT = 64;  // queries per tile of the dkdv loop
 
 // TI: storage type of q / k / v, TD: of dO (float or bf16s).
-template <int HD, typename TI = float, typename TD = float>
+template <int HD, typename TI = float, typename TD = float, bool LENS = false>
 __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dkdv_mf_kernel(
     const TI* __restrict__ q, const TI* __restrict__ k, const TI* __restrict__ v,
     const TD* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ delta,
     float* __restrict__ dk, float* __restrict__ dv, AttnStridesMF sq, AttnStridesMF sk, AttnStridesMF sv,
     AttnStridesMF sd, AttnStridesMF sdk, AttnStridesMF sdv, int64_t H, int64_t Lq, int64_t Lk, int causal,
-    float scale) {
+    float scale, const int32_t* __restrict__ lens = nullptr) {
   typedef BwdCfg<HD> C;
   constexpr int NH = HD / 64;
   __shared__ __attribute__((aligned(16))) unsigned short Qr[2][NH * HALF], Qt[2][NH * HALF];
@@ -581,13 +629,24 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dkdv_mf_kernel(
   const float* lb = lse + ((int64_t)b * H + h) * Lq;
   const float* db = delta + ((int64_t)b * H + h) * Lq;
   const float c = scale * LOG2E;
+  int64_t ql = Lq, kl = Lk;  // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (k0 >= kl || ql == 0) {
+      if (key < Lk) {
+        zero_rowT<HD>(dk + b * sdk.b + h * sdk.h + key * sdk.l, hi);
+        zero_rowT<HD>(dv + b * sdv.b + h * sdv.h + key * sdv.l, hi);
+      }
+      return;
+    }
+  }
 
   bf16x8 kf[HD / 16], vf[HD / 16];
-  row_frags<HD>(k + b * sk.b + h * sk.h, sk.l, key, Lk, hi, kf);
-  row_frags<HD>(v + b * sv.b + h * sv.h, sv.l, key, Lk, hi, vf);
+  row_frags<HD>(k + b * sk.b + h * sk.h, sk.l, key, kl, hi, kf);
+  row_frags<HD>(v + b * sv.b + h * sv.h, sv.l, key, kl, hi, vf);
 
   const int64_t qt0 = causal ? k0 / BQT : 0;  // causal: tiles entirely before the block's keys are masked
-  const int ntiles = (int)((Lq + BQT - 1) / BQT - qt0);
+  const int ntiles = (int)((ql + BQT - 1) / BQT - qt0);
   const int srow = tid >> 3, sc = tid & 7;
   Row8<TI> qa[C::RI][NH];
   Row8<TD> ga[C::RI][NH];
@@ -598,12 +657,12 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dkdv_mf_kernel(
     for (int i = 0; i < C::RI; ++i)
 #pragma unroll
       for (int hf = 0; hf < NH; ++hf) {
-        stage_load(qb, sq, q0 + srow + i * (C::NT / 8), Lq, hf, sc, qa[i][hf]);
-        stage_load(gb, sd, q0 + srow + i * (C::NT / 8), Lq, hf, sc, ga[i][hf]);
+        stage_load(qb, sq, q0 + srow + i * (C::NT / 8), ql, hf, sc, qa[i][hf]);
+        stage_load(gb, sd, q0 + srow + i * (C::NT / 8), ql, hf, sc, ga[i][hf]);
       }
     if (tid < BQT) {
       const int64_t qi = q0 + tid;
-      ld = qi < Lq ? make_float2(lb[qi] * LOG2E, db[qi]) : make_float2(INFINITY, 0.f);
+      ld = qi < ql ? make_float2(lb[qi] * LOG2E, db[qi]) : make_float2(INFINITY, 0.f);
     }
   };
   auto stage_st = [&](int buf) {
@@ -695,18 +754,25 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dkdv_mf_kernel(
     __syncthreads();
   }
 
-  if (key < Lk) {
+  if (key < kl) {
     store_rowT<HD>(dk + b * sdk.b + h * sdk.h + key * sdk.l, dkacc, scale, hi);
     store_rowT<HD>(dv + b * sdv.b + h * sdv.h + key * sdv.l, dvacc, 1.f, hi);
   }
+  if constexpr (LENS) {
+    if (key >= kl && key < Lk) {
+      zero_rowT<HD>(dk + b * sdk.b + h * sdk.h + key * sdk.l, hi);
+      zero_rowT<HD>(dv + b * sdv.b + h * sdv.h + key * sdv.l, hi);
+    }
+  }
 }
 
-template <int HD, typename TI = float, typename TD = float>
+template <int HD, typename TI = float, typename TD = float, bool LENS = false>
 __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dq_mf_kernel(
     const TI* __restrict__ q, const TI* __restrict__ k, const TI* __restrict__ v,
     const TD* __restrict__ dO, const float* __restrict__ lse, const float* __restrict__ delta,
     float* __restrict__ dq, AttnStridesMF sq, AttnStridesMF sk, AttnStridesMF sv, AttnStridesMF sd,
-    AttnStridesMF sdq, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale) {
+    AttnStridesMF sdq, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale,
+    const int32_t* __restrict__ lens = nullptr) {
   typedef BwdCfg<HD> C;
   constexpr int NH = HD / 64;
   __shared__ __attribute__((aligned(16))) unsigned short Kr[2][NH * HALF], Kt2[2][NH * HALF], Vr[2][NH * HALF];
@@ -721,15 +787,23 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dq_mf_kernel(
   const TI* kbp = k + b * sk.b + h * sk.h;
   const TI* vbp = v + b * sv.b + h * sv.h;
   const float c = scale * LOG2E;
+  int64_t ql = Lq, kl = Lk;  // row limits
+  if constexpr (LENS) {
+    lens_pair(lens, b, Lq, Lk, ql, kl);
+    if (q0 >= ql || kl == 0) {
+      if (qi < Lq) zero_rowT<HD>(dq + b * sdq.b + h * sdq.h + qi * sdq.l, hi);
+      return;
+    }
+  }
 
   bf16x8 qf[HD / 16], gf[HD / 16];
-  row_frags<HD>(q + b * sq.b + h * sq.h, sq.l, qi, Lq, hi, qf);
-  row_frags<HD>(dO + b * sd.b + h * sd.h, sd.l, qi, Lq, hi, gf);
-  const float l2 = qi < Lq ? lse[((int64_t)b * H + h) * Lq + qi] * LOG2E : 0.f;
-  const float dl = qi < Lq ? delta[((int64_t)b * H + h) * Lq + qi] : 0.f;
+  row_frags<HD>(q + b * sq.b + h * sq.h, sq.l, qi, ql, hi, qf);
+  row_frags<HD>(dO + b * sd.b + h * sd.h, sd.l, qi, ql, hi, gf);
+  const float l2 = qi < ql ? lse[((int64_t)b * H + h) * Lq + qi] * LOG2E : 0.f;
+  const float dl = qi < ql ? delta[((int64_t)b * H + h) * Lq + qi] : 0.f;
 
-  int64_t kend = Lk;
-  if (causal) kend = min(Lk, q0 + 32 * C::NW);
+  int64_t kend = kl;
+  if (causal) kend = min(kl, q0 + 32 * C::NW);
   const int ntiles = (int)((kend + KT - 1) / KT);
   const int skey = tid >> 3, sc = tid & 7;
 
@@ -739,8 +813,8 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dq_mf_kernel(
     for (int i = 0; i < C::RI; ++i)
 #pragma unroll
       for (int hf = 0; hf < NH; ++hf) {
-        stage_load(kbp, sk, k0 + skey + i * (C::NT / 8), Lk, hf, sc, ka[i][hf]);
-        stage_load(vbp, sv, k0 + skey + i * (C::NT / 8), Lk, hf, sc, va[i][hf]);
+        stage_load(kbp, sk, k0 + skey + i * (C::NT / 8), kl, hf, sc, ka[i][hf]);
+        stage_load(vbp, sv, k0 + skey + i * (C::NT / 8), kl, hf, sc, va[i][hf]);
       }
   };
   auto stage_st = [&](int buf) {
@@ -780,8 +854,8 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dq_mf_kernel(
       dot_rows<HD>(pacc[kb2], Vr[buf], 32 * kb2 + j, hi, gf);
     }
     const bool need_mask =
-        __builtin_amdgcn_readfirstlane((int)((k0 + KT > Lk) || (causal && k0 + KT - 1 > q0 + wid * 32))) != 0;
-    const int lim = need_mask ? (int)min(min(Lk - k0, (int64_t)KT), causal ? qi - k0 + 1 : (int64_t)KT) : KT;
+        __builtin_amdgcn_readfirstlane((int)((k0 + KT > kl) || (causal && k0 + KT - 1 > q0 + wid * 32))) != 0;
+    const int lim = need_mask ? (int)min(min(kl - k0, (int64_t)KT), causal ? qi - k0 + 1 : (int64_t)KT) : KT;
     bf16x8 sb[2][2];
 #pragma unroll
     for (int kb2 = 0; kb2 < 2; ++kb2)
@@ -816,7 +890,10 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dq_mf_kernel(
     __syncthreads();
   }
 
-  if (qi < Lq) store_rowT<HD>(dq + b * sdq.b + h * sdq.h + qi * sdq.l, dqacc, scale, hi);
+  if (qi < ql) store_rowT<HD>(dq + b * sdq.b + h * sdq.h + qi * sdq.l, dqacc, scale, hi);
+  if constexpr (LENS) {
+    if (qi >= ql && qi < Lq) zero_rowT<HD>(dq + b * sdq.b + h * sdq.h + qi * sdq.l, hi);
+  }
 }
 
 }  // namespace amf
@@ -824,10 +901,10 @@ __global__ __launch_bounds__(BwdCfg<HD>::NT, 1) void attn_bwd_dq_mf_kernel(
 // forward kernel for HD = 64 (asrx_set_attn_variant): 1 attn_fwd_sp_kernel (default), 0 attn_fwd_mf_kernel
 static int g_attn_fwd_variant = 1;
 
-template <int HD, typename TI, typename TO>
+template <int HD, typename TI, typename TO, bool LENS = false>
 static void attn_fwd_mf_t(const void* q, AttnStridesMF Sq, const void* k, AttnStridesMF Sk, const void* v,
                           AttnStridesMF Sv, void* o, AttnStridesMF So, float* lse, int64_t B, int64_t H, int64_t Lq,
-                          int64_t Lk, int causal, float scale, hipStream_t stream) {
+                          int64_t Lk, int causal, float scale, hipStream_t stream, const int32_t* lens = nullptr) {
   const TI *qq = (const TI*)q, *kk = (const TI*)k, *vv = (const TI*)v;
   TO* oo = (TO*)o;
   dim3 g((unsigned)((Lq + amf::QB - 1) / amf::QB), (unsigned)H, (unsigned)B);
@@ -836,27 +913,29 @@ static void attn_fwd_mf_t(const void* q, AttnStridesMF Sq, const void* k, AttnSt
   // and s_setprio variants)
   if (HD == 64 && g_attn_fwd_variant == 1) {
     if (g.x > 1)
-      amf::attn_fwd_sp_kernel<true, TI, TO><<<dim3((unsigned)((int64_t)g.x * g.y * g.z)), amf::NTHR, 0, stream>>>(
-          qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H, Lq, Lk, causal, scale);
+      amf::attn_fwd_sp_kernel<true, TI, TO, LENS><<<dim3((unsigned)((int64_t)g.x * g.y * g.z)), amf::NTHR, 0,
+                                                    stream>>>(qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H, Lq, Lk, causal,
+                                                              scale, lens);
     else
-      amf::attn_fwd_sp_kernel<false, TI, TO><<<g, amf::NTHR, 0, stream>>>(qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H, Lq,
-                                                                          Lk, causal, scale);
+      amf::attn_fwd_sp_kernel<false, TI, TO, LENS><<<g, amf::NTHR, 0, stream>>>(qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H,
+                                                                                Lq, Lk, causal, scale, lens);
   } else if (HD == 64 && g.x > 1)
-    amf::attn_fwd_mf_kernel<HD, 1, true, false, TI, TO><<<dim3((unsigned)((int64_t)g.x * g.y * g.z)), amf::NTHR, 0,
-                                                          stream>>>(qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H, Lq, Lk,
-                                                                    causal, scale);
+    amf::attn_fwd_mf_kernel<HD, 1, true, false, TI, TO, LENS><<<dim3((unsigned)((int64_t)g.x * g.y * g.z)), amf::NTHR,
+                                                                0, stream>>>(qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H, Lq,
+                                                                             Lk, causal, scale, lens);
   else
-    amf::attn_fwd_mf_kernel<HD, 1, false, false, TI, TO><<<g, amf::NTHR, 0, stream>>>(qq, kk, vv, oo, lse, Sq, Sk, Sv,
-                                                                                     So, H, Lq, Lk, causal, scale);
+    amf::attn_fwd_mf_kernel<HD, 1, false, false, TI, TO, LENS><<<g, amf::NTHR, 0, stream>>>(
+        qq, kk, vv, oo, lse, Sq, Sk, Sv, So, H, Lq, Lk, causal, scale, lens);
 }
 
-// bf16 flash-attention forward (see header); called by asrx_attn_fwd for prec == PREC_BF16.  io: bit 0
-// q / k / v stored bf16, bit 1 o stored bf16.
-int attn_fwd_mf(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
-                const int64_t* sv, void* o, const int64_t* so, float* lse, int64_t B, int64_t H, int64_t Lq,
-                int64_t Lk, int64_t hd, int causal, float scale, hipStream_t stream) {
+template <bool LENS>
+static int attn_fwd_mf_io(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
+                          const int64_t* sv, void* o, const int64_t* so, float* lse, const int32_t* lens, int64_t B,
+                          int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale,
+                          hipStream_t stream) {
   AttnStridesMF Sq{sq[0], sq[1], sq[2]}, Sk{sk[0], sk[1], sk[2]}, Sv{sv[0], sv[1], sv[2]}, So{so[0], so[1], so[2]};
-#define ASRX_AF(HDV, TI, TO) attn_fwd_mf_t<HDV, TI, TO>(q, Sq, k, Sk, v, Sv, o, So, lse, B, H, Lq, Lk, causal, scale, stream)
+#define ASRX_AF(HDV, TI, TO) \
+  attn_fwd_mf_t<HDV, TI, TO, LENS>(q, Sq, k, Sk, v, Sv, o, So, lse, B, H, Lq, Lk, causal, scale, stream, lens)
   if (hd == 64) {
     switch (io & 3) {
       case 0: ASRX_AF(64, float, float); break;
@@ -876,35 +955,51 @@ int attn_fwd_mf(int io, const void* q, const int64_t* sq, const void* k, const i
   return 0;
 }
 
-template <int HD, typename TI, typename TD>
+// bf16 flash-attention forward (see header); called by asrx_attn_fwd for prec == PREC_BF16.  io: bit 0
+// q / k / v stored bf16, bit 1 o stored bf16.
+int attn_fwd_mf(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
+                const int64_t* sv, void* o, const int64_t* so, float* lse, int64_t B, int64_t H, int64_t Lq,
+                int64_t Lk, int64_t hd, int causal, float scale, hipStream_t stream) {
+  return attn_fwd_mf_io<false>(io, q, sq, k, sk, v, sv, o, so, lse, nullptr, B, H, Lq, Lk, hd, causal, scale, stream);
+}
+
+// the same kernel choice (launch extents, variant) with per-sample {q_len, k_len} limits from `lens` (B x 2
+// device ints): the LENS instantiations; called by asrx_lattn_fwd (attn_lens.hip)
+int attn_fwd_mf_lens(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
+                     const int64_t* sv, void* o, const int64_t* so, float* lse, const int32_t* lens, int64_t B,
+                     int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale, hipStream_t stream) {
+  return attn_fwd_mf_io<true>(io, q, sq, k, sk, v, sv, o, so, lse, lens, B, H, Lq, Lk, hd, causal, scale, stream);
+}
+
+template <int HD, typename TI, typename TD, bool LENS = false>
 static void attn_bwd_mf_t(const void* q, AttnStridesMF Sq, const void* k, AttnStridesMF Sk, const void* v,
                           AttnStridesMF Sv, const void* dO, AttnStridesMF Sd, const float* lse, const float* delta,
                           float* dq, AttnStridesMF Sdq, float* dk, AttnStridesMF Sdk, float* dv, AttnStridesMF Sdv,
-                          int64_t B, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale, hipStream_t stream) {
+                          int64_t B, int64_t H, int64_t Lq, int64_t Lk, int causal, float scale, hipStream_t stream,
+                          const int32_t* lens = nullptr) {
   typedef amf::BwdCfg<HD> C;
   const TI *qq = (const TI*)q, *kk = (const TI*)k, *vv = (const TI*)v;
   const TD* gg = (const TD*)dO;
   const int64_t rows_per_wg = 32 * C::NW;
   dim3 gk((unsigned)(((Lk + rows_per_wg - 1) / rows_per_wg) * H * B));
-  amf::attn_bwd_dkdv_mf_kernel<HD, TI, TD><<<gk, C::NT, 0, stream>>>(qq, kk, vv, gg, lse, delta, dk, dv, Sq, Sk, Sv, Sd,
-                                                                     Sdk, Sdv, H, Lq, Lk, causal, scale);
+  amf::attn_bwd_dkdv_mf_kernel<HD, TI, TD, LENS><<<gk, C::NT, 0, stream>>>(qq, kk, vv, gg, lse, delta, dk, dv, Sq, Sk, Sv,
+                                                                           Sd, Sdk, Sdv, H, Lq, Lk, causal, scale, lens);
   dim3 gq((unsigned)(((Lq + rows_per_wg - 1) / rows_per_wg) * H * B));
-  amf::attn_bwd_dq_mf_kernel<HD, TI, TD><<<gq, C::NT, 0, stream>>>(qq, kk, vv, gg, lse, delta, dq, Sq, Sk, Sv, Sd, Sdq,
-                                                                   H, Lq, Lk, causal, scale);
+  amf::attn_bwd_dq_mf_kernel<HD, TI, TD, LENS><<<gq, C::NT, 0, stream>>>(qq, kk, vv, gg, lse, delta, dq, Sq, Sk, Sv, Sd,
+                                                                         Sdq, H, Lq, Lk, causal, scale, lens);
 }
 
-// bf16 flash-attention backward (dkdv + dq kernels above); delta = rowsum(dO * O) already computed.
-// io: bit 0 q / k / v stored bf16, bit 2 dO stored bf16.
-int attn_bwd_mf(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
-                const int64_t* sv, const void* dO, const int64_t* sd, const float* lse, const float* delta,
-                float* dq, const int64_t* sdq, float* dk, const int64_t* sdk, float* dv, const int64_t* sdv,
-                int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale,
-                hipStream_t stream) {
+template <bool LENS>
+static int attn_bwd_mf_io(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
+                          const int64_t* sv, const void* dO, const int64_t* sd, const float* lse, const float* delta,
+                          float* dq, const int64_t* sdq, float* dk, const int64_t* sdk, float* dv, const int64_t* sdv,
+                          const int32_t* lens, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal,
+                          float scale, hipStream_t stream) {
   AttnStridesMF Sq{sq[0], sq[1], sq[2]}, Sk{sk[0], sk[1], sk[2]}, Sv{sv[0], sv[1], sv[2]}, Sd{sd[0], sd[1], sd[2]};
   AttnStridesMF Sdq{sdq[0], sdq[1], sdq[2]}, Sdk{sdk[0], sdk[1], sdk[2]}, Sdv{sdv[0], sdv[1], sdv[2]};
-#define ASRX_AB(HDV, TI, TD)                                                                                       \
-  attn_bwd_mf_t<HDV, TI, TD>(q, Sq, k, Sk, v, Sv, dO, Sd, lse, delta, dq, Sdq, dk, Sdk, dv, Sdv, B, H, Lq, Lk, causal, \
-                             scale, stream)
+#define ASRX_AB(HDV, TI, TD)                                                                                      \
+  attn_bwd_mf_t<HDV, TI, TD, LENS>(q, Sq, k, Sk, v, Sv, dO, Sd, lse, delta, dq, Sdq, dk, Sdk, dv, Sdv, B, H, Lq, Lk, \
+                                   causal, scale, stream, lens)
   const int sel = (io & 1) | ((io >> 1) & 2);
   if (hd == 64) {
     switch (sel) {
@@ -923,6 +1018,27 @@ int attn_bwd_mf(int io, const void* q, const int64_t* sq, const void* k, const i
   }
 #undef ASRX_AB
   return 0;
+}
+
+// bf16 flash-attention backward (dkdv + dq kernels above); delta = rowsum(dO * O) already computed.
+// io: bit 0 q / k / v stored bf16, bit 2 dO stored bf16.
+int attn_bwd_mf(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
+                const int64_t* sv, const void* dO, const int64_t* sd, const float* lse, const float* delta,
+                float* dq, const int64_t* sdq, float* dk, const int64_t* sdk, float* dv, const int64_t* sdv,
+                int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale,
+                hipStream_t stream) {
+  return attn_bwd_mf_io<false>(io, q, sq, k, sk, v, sv, dO, sd, lse, delta, dq, sdq, dk, sdk, dv, sdv, nullptr, B, H,
+                               Lq, Lk, hd, causal, scale, stream);
+}
+
+// the LENS instantiations of the two backward kernels (asrx_lattn_bwd, attn_lens.hip)
+int attn_bwd_mf_lens(int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk, const void* v,
+                     const int64_t* sv, const void* dO, const int64_t* sd, const float* lse, const float* delta,
+                     float* dq, const int64_t* sdq, float* dk, const int64_t* sdk, float* dv, const int64_t* sdv,
+                     const int32_t* lens, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal,
+                     float scale, hipStream_t stream) {
+  return attn_bwd_mf_io<true>(io, q, sq, k, sk, v, sv, dO, sd, lse, delta, dq, sdq, dk, sdk, dv, sdv, lens, B, H, Lq,
+                              Lk, hd, causal, scale, stream);
 }
 
 }  // namespace asrx

@@ -60,6 +60,18 @@ int check_launch(const char* what);
 // ---------------------------------------------------------------- device helpers
 namespace asrx {
 
+// Attention LENS kernels (attn.hip, attn_mf.hip): sample b's {q_len, k_len} of the (B, 2) device table, one
+// workgroup-uniform load each (b comes from the block index), clamped to the launch extents so that a bad
+// table cannot address past them.  The launch extents keep the grid, the tensor addressing and the lse /
+// delta row offsets; ql / kl take their place as row limits.
+__device__ __forceinline__ void lens_pair(const int32_t* lens, int b, int64_t Lq, int64_t Lk, int64_t& ql,
+                                          int64_t& kl) {
+  const int a = __builtin_amdgcn_readfirstlane(lens[2 * (int64_t)b]);
+  const int c = __builtin_amdgcn_readfirstlane(lens[2 * (int64_t)b + 1]);
+  ql = min(max((int64_t)a, (int64_t)0), Lq);
+  kl = min(max((int64_t)c, (int64_t)0), Lk);
+}
+
 __device__ __forceinline__ float gelu_f(float x) {  // exact (erf) GELU, nn.GELU() default
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
 }

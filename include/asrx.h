@@ -238,6 +238,23 @@ int asrx_attn_bwd(int prec, const float* q, const int64_t* sq, const float* k, c
                   const float* lse, float* delta_ws, float* dq, const int64_t* sdq, float* dk, const int64_t* sdk,
                   float* dv, const int64_t* sdv, int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd,
                   int causal, float scale, asrx_stream_t stream);
+/* Attention with per-sample lengths: the two storage-typed entry points above plus `lens`, a device table of
+ * B x 2 int32 {q_len, k_len} per sample.  Sample b's query rows [0, q_len) attend to its keys [0, k_len) exactly
+ * as a B = 1 call with those extents does, bit for bit; O, lse and dQ rows at or past q_len and dK, dV rows at or
+ * past k_len are stored as zeros, and nothing live depends on what q / k / v / dO hold there (NaN included).
+ * Each length is clamped to [0, Lq] / [0, Lk], which remain the launch extents (addressing, the lse rows and
+ * the delta_ws workspace, unspecified on dead rows).  prec 0 or 1: the fp8 forward is refused.  The checks of
+ * the uniform entry points apply in the same order and words, then `lens` must be non-null and 4-byte
+ * aligned; every check answers before anything is launched. */
+int asrx_lattn_fwd(int prec, int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk,
+                   const void* v, const int64_t* sv, void* o, const int64_t* so, float* lse, const int32_t* lens,
+                   int64_t B, int64_t H, int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale,
+                   asrx_stream_t stream);
+int asrx_lattn_bwd(int prec, int io, const void* q, const int64_t* sq, const void* k, const int64_t* sk,
+                   const void* v, const int64_t* sv, const void* o, const int64_t* so, const void* dO,
+                   const int64_t* sd, const float* lse, float* delta_ws, float* dq, const int64_t* sdq, float* dk,
+                   const int64_t* sdk, float* dv, const int64_t* sdv, const int32_t* lens, int64_t B, int64_t H,
+                   int64_t Lq, int64_t Lk, int64_t hd, int causal, float scale, asrx_stream_t stream);
 
 /* ---- LayerNorm over the last dim: nn.LayerNorm in MSheath (model.py:405, 427) and the channel
  *      LayerNorm of the encoder (essentials.py:110-113) on channels-last rows. ------------------ */
