@@ -71,6 +71,7 @@ SIGNATURES = {
     "asrx_ce_fwd1": (_i32, [_p] * 6 + [_i64, _i64, _p]),
     "asrx_ce_bwd2": (_i32, [_p] * 6 + [_i64, _i64, _p]),
     "asrx_bn_running": (_i32, [_p] * 5 + [_i64, _i64, _i64, _f32, _f32, _p]),
+    "asrx_bn_running_lens": (_i32, [_p] * 6 + [_i64, _i64, _i64, _f32, _f32, _p]),
     "asrx_rsqrt_eps": (_i32, [_p, _p, _i64, _f32, _p]),
     "asrx_conv3_weight": (_i32, [_p, _p, _i64, _i64] + [_p] * 6),
     "asrx_conv3_weight_bwd": (_i32, [_p] * 4 + [_i64, _i64] + [_p] * 3),
@@ -151,6 +152,14 @@ SIGNATURES = {
     "asrx_dwconv_pre_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
     "asrx_bn_silu_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _i32, _p]),
     "asrx_bn_silu_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "asrx_act_lens_fwd": (_i32, [_p, _p, _p, _i64, _i64, _i64, _i32, _p]),
+    "asrx_act_lens_bwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
+    "asrx_act_dropout_lens_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _u32, _f32, _i32, _i32, _p]),
+    "asrx_act_dropout_lens_bwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _u32, _f32, _i32, _i32, _p]),
+    "asrx_dwconv_lens_fwd": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p]),
+    "asrx_dwconv_pre_lens_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
+    "asrx_bn_silu_lens_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _i32, _p]),
+    "asrx_bn_silu_lens_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_stem1_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_stem1_bwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_embed_fwd": (_i32, [_p, _p, _p, _i64, _i64, _p]),

@@ -122,17 +122,20 @@ class ConvLite(nn.Module):
         self.point2 = nn.Conv1d(dims, dims, kernel_size=1)
         self.dropout = nn.Dropout(0.1)
 
-    def run(self, x, noise: NoiseCtx, site: str, sid_base: int):
-        """model.py:109-118 on channels-last (B, T, D)."""
+    def run(self, x, noise: NoiseCtx, site: str, sid_base: int, lens=None):
+        """model.py:109-118 on channels-last (B, T, D).  lens (ops.seq_lens): per-sample lengths -- the k15 conv
+        stops at each sample's end and the BatchNorm statistics run over its live rows; the 1x1 convs, the eval-mode
+        BatchNorm and the dropout are row-local and still compute the pad rows (finite, unread)."""
         D = x.shape[-1]
         x = ops.fork(x)  # read by point1 and the residual add
         res = x
         y = ops.linear(x, self.point1.weight, self.point1.bias)  # (2D, D, 1) leaf: gradient straight into it
-        y = ops.glu_dwconv(y, self.depth.weight, self.depth.bias)  # GLU's backward runs in the conv's dgrad kernel
+        # GLU's backward runs in the conv's dgrad kernel
+        y = ops.glu_dwconv(y, self.depth.weight, self.depth.bias, lens=lens)
         if self.training:  # BatchNorm apply + SiLU in one pass each way
             stats = []
-            y = ops.batch_norm_silu(y, self.bn.weight, self.bn.bias, self.bn.eps, stats)
-            self._update_running(stats[0], y.shape[1])
+            y = ops.batch_norm_silu(y, self.bn.weight, self.bn.bias, self.bn.eps, stats, lens=lens)
+            self._update_running(stats[0], y.shape[1], lens)
         else:
             y = ops.batch_norm_silu_eval(y, self.bn.weight, self.bn.bias, self.bn.running_mean,
                                          self.bn.running_var, self.bn.eps)
@@ -142,13 +145,19 @@ class ConvLite(nn.Module):
         return ops.add(res, y)
 
     @torch.no_grad()
-    def _update_running(self, stats, T):
+    def _update_running(self, stats, T, lens=None):
         # batch-1 semantics: one update per clip would be applied by the reference; here the mean of
         # the per-clip statistics is applied once per stream group (running stats do not affect the
         # train-mode output).  One kernel (asrx_bn_running) instead of the ATen update chain.
+        # With lens, each clip's variance is unbiased by its own T_b / (T_b - 1).
         mean, rstd = stats
         B, C = mean.shape
         bn = self.bn
+        if lens is not None and not lens.check(B, T, mean.device):
+            lib.call("asrx_bn_running_lens", lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean),
+                     lib.ptr(bn.running_var), lib.ptr(bn.num_batches_tracked), lib.ptr(lens.table), B, C, T,
+                     float(bn.eps), float(bn.momentum), lib.stream())
+            return
         lib.call("asrx_bn_running", lib.ptr(mean), lib.ptr(rstd), lib.ptr(bn.running_mean), lib.ptr(bn.running_var),
                  lib.ptr(bn.num_batches_tracked), B, C, T, float(bn.eps), float(bn.momentum), lib.stream())
 
@@ -185,28 +194,44 @@ class AudioEncoder(nn.Module):
             return ops.conv3(xt, self.conv1[0], out=out)
         return ops.Stem1.apply(x.reshape(B, T), self.conv2[0].weight, self.conv2[0].bias, out)
 
-    def layers(self, x, noise: NoiseCtx, sid_base: int):
+    def layers(self, x, noise: NoiseCtx, sid_base: int, lens=None):
+        """The encoder layers on (B, T, D) and the positional table.  lens (ops.seq_lens, B entries): sample b's
+        rows [0, T_b) come out as for x[b:b+1, :T_b] alone with sid_base + b; the ops that reach across rows take
+        the lengths, and each k3 GEMM conv reads zeros in the pad rows because its producer (the leading GELU, the
+        previous layer's tail) stores them.  Pad rows of the result hold the positional table only."""
+        if lens is not None and lens.check(x.shape[0], x.shape[1], x.device):
+            lens = None  # every sample full length: the uniform path
         n = len(self.encoder)
         fused_lead = False  # the previous layer's fused tail already applied this layer's leading GELU
         for l, layer in enumerate(self.encoder):
             if not fused_lead:
-                x = ops.act(x, "gelu")
+                x = ops.act(x, "gelu", lens=lens)
             fused_lead = False
             x = ops.conv3(x, layer[1])
             x = ops.layer_norm(x, layer[2].gamma, layer[2].beta, layer[2].eps)
-            x = layer[3].run(x, noise, f"enc.L{l}", sid_base)
-            x = ops.act_dwconv(x, "gelu", layer[5].weight, layer[5].bias)  # GELU's backward: conv's dgrad kernel
+            x = layer[3].run(x, noise, f"enc.L{l}", sid_base, lens=lens)
+            # GELU's backward: conv's dgrad kernel
+            x = ops.act_dwconv(x, "gelu", layer[5].weight, layer[5].bias, lens=lens)
             if self.training:  # GELU -> Dropout(0.1) [-> next layer's GELU] in one kernel each way
                 fused_lead = l + 1 < n
                 x = ops.act_dropout(x, "gelu", sid_base, noise.key(f"enc.L{l}.dr"), 0.1,
-                                         "gelu" if fused_lead else "none")
+                                         "gelu" if fused_lead else "none", lens=lens)
             else:
-                x = ops.act(x, "gelu")
+                x = ops.act(x, "gelu", lens=lens)
         return ops.add_rows(x, sinusoids(x.shape[1], x.shape[2], x.device))
 
-    def encode(self, streams, noise: NoiseCtx, B: int):
+    def encode(self, streams, noise: NoiseCtx, B: int, lens=None):
         """streams: list of 3 (B, C, T) tensors (a, b, c).  Returns 3 (B, T, D) encodings; streams
-        of equal length share one batched pass (sample ids stay s*B + b)."""
+        of equal length share one batched pass (sample ids stay s*B + b).
+
+        lens: per-sample lengths of a zero-padded batch, one entry per stream: None (every sample full length),
+        host integers (a list, a tuple or a CPU tensor) or an ops.seq_lens table of that stream's B samples; a
+        length above the stream's T is refused.  Sample b of stream s then comes out on its rows [0, T_b) as that
+        sample alone, unpadded, would (bit for bit), and the pad rows of the returned encodings hold the
+        positional table only: finite and independent of the input.  Contract on the input: the pad frames of the
+        streams hold zeros, as mel.logmel_ragged and the collator write them -- the stem's last live row reads
+        frame T_b.  This is not checked (reading the features back would synchronise)."""
+        slens = self._stream_lens(streams, lens)
         # runs of consecutive equal-length streams share one pass: their stems write straight into the
         # row blocks of one group buffer (no concatenation copy)
         lens = [s.shape[-1] for s in streams]
@@ -226,10 +251,35 @@ class AudioEncoder(nn.Module):
                     parts.append(self.stem(s, out=buf[r0:r0 + b]))
                     r0 += b
                 x = ops.join_group(buf, parts)
-            y = self.layers(x, noise, i * B)
+            y = self.layers(x, noise, i * B, self._group_lens(streams[i:j], slens[i:j]))
             out[i:j] = ops.split_rows(y, j - i)
             i = j
         return out
+
+    @staticmethod
+    def _stream_lens(streams, lens):
+        """encode's lens -> one ops.SeqLens or None per stream, checked against the stream's extents."""
+        if lens is None:
+            return [None] * len(streams)
+        if len(lens) != len(streams):
+            raise ValueError(f"encode: lens holds {len(lens)} entries for {len(streams)} streams")
+        out = []
+        for s, sl in zip(streams, lens):
+            if sl is not None:
+                if not isinstance(sl, ops.SeqLens):
+                    sl = ops.seq_lens(sl, device=s.device)
+                sl.check(s.shape[0] if s.dim() == 3 else 1, s.shape[-1], s.device)
+            out.append(sl)
+        return out
+
+    @staticmethod
+    def _group_lens(streams, slens):
+        """The table of a group of equal-padded-length streams: the members' tables joined on the device, a member
+        without lengths counting as full length; None when no member has lengths."""
+        if all(sl is None for sl in slens):
+            return None
+        return ops.SeqLens.join([ops.SeqLens.full(s.shape[0] if s.dim() == 3 else 1, s.shape[-1], s.device)
+                                 if sl is None else sl for s, sl in zip(streams, slens)])
 
 
 # ------------------------------------------------------------------------------- attention

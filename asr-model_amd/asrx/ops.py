@@ -788,18 +788,18 @@ class AttnLens:
         return min(self.q_lens) == Lq and min(self.k_lens) == Lk
 
 
-def _host_lens(x, what):
+def _host_lens(x, what, who="attn_lens"):
     if isinstance(x, torch.Tensor):
         if x.device.type != "cpu":
-            raise TypeError(f"attn_lens: {what} is a device tensor (reading it would synchronise): pass host integers")
+            raise TypeError(f"{who}: {what} is a device tensor (reading it would synchronise): pass host integers")
         x = x.tolist()
     if not isinstance(x, (list, tuple)):
-        raise TypeError(f"attn_lens: {what} must be a list, a tuple or a CPU tensor of integers")
+        raise TypeError(f"{who}: {what} must be a list, a tuple or a CPU tensor of integers")
     out = tuple(int(a) for a in x)
     if any(a != b for a, b in zip(out, x)):
-        raise TypeError(f"attn_lens: {what} must hold integers")
+        raise TypeError(f"{who}: {what} must hold integers")
     if not out or min(out) < 1:
-        raise ValueError(f"attn_lens: {what} must hold lengths >= 1, got {list(x)}")
+        raise ValueError(f"{who}: {what} must hold lengths >= 1, got {list(x)}")
     return out
 
 
@@ -816,6 +816,72 @@ def attn_lens(q_lens, k_lens=None, device=None) -> AttnLens:
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     host = torch.tensor([ql, kl], dtype=torch.int32).t().contiguous().pin_memory()
     return AttnLens(ql, kl, host.to(dev, non_blocking=True))
+
+
+class SeqLens:
+    """Per-sample row counts of one (B, T, C) batch (seq_lens): the host tuple `lens` and `table`, the int32 (B,)
+    device table the encoder's LENS kernels read."""
+
+    __slots__ = ("lens", "table", "B")
+
+    def __init__(self, lens, table):
+        self.lens, self.table, self.B = tuple(lens), table, len(lens)
+
+    def check(self, B, T, device) -> bool:
+        """Host check against a call's extents (ValueError); -> whether every sample is full length."""
+        if self.B != B:
+            raise ValueError(f"seq_lens: lens holds {self.B} samples, the batch {B}")
+        if max(self.lens) > T:
+            raise ValueError(f"seq_lens: lens up to {max(self.lens)} exceed the sequence length {T}")
+        if self.table.device != device:
+            raise ValueError(f"seq_lens: lens table on {self.table.device}, tensors on {device}")
+        return min(self.lens) == T
+
+    @staticmethod
+    def full(B, T, device) -> "SeqLens":
+        """B samples of full length T; the table is filled on the device (capturable)."""
+        return SeqLens((int(T),) * B, torch.full((B,), int(T), dtype=torch.int32, device=device))
+
+    @staticmethod
+    def join(parts) -> "SeqLens":
+        """The table of a stream group: the members' samples one after the other.  A device-side concatenation of
+        the members' tables (no host copy), so it may run under graph capture."""
+        parts = list(parts)
+        if len(parts) == 1:
+            return parts[0]
+        return SeqLens(sum((p.lens for p in parts), ()), torch.cat([p.table for p in parts]))
+
+
+def seq_lens(lens, device=None) -> SeqLens:
+    """Per-sample lengths for the encoder ops (act, act_dropout, glu_dwconv, act_dwconv, batch_norm_silu with
+    lens=) and AudioEncoder.encode: host integers >= 1 (a list, a tuple or a CPU tensor; a device tensor raises
+    TypeError, reading it would synchronise).  The (B,) int32 device table is filled once through pinned memory
+    with a non-blocking copy: make one per batch, outside graph capture, and reuse it for every call of the step."""
+    ls = _host_lens(lens, "lens", "seq_lens")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    host = torch.tensor(ls, dtype=torch.int32).pin_memory()
+    return SeqLens(ls, host.to(dev, non_blocking=True))
+
+
+def _live_lens(lens, x, what, *ps):
+    """lens of an encoder op on x (B, T, C) -> None when absent or every sample is full length (the uniform path,
+    untouched), else lens after the checks of the LENS kernels: they exist in the fused float4 form only, and a
+    call they cannot take is an error, never a fall-back to kernels that would ignore the lengths."""
+    if lens is None:
+        return None
+    if not isinstance(lens, SeqLens):
+        raise TypeError(f"{what}: lens must come from ops.seq_lens, got {type(lens).__name__}")
+    if x.dim() != 3:
+        raise ValueError(f"{what}: lens needs a (B, T, C) tensor, got {tuple(x.shape)}")
+    if lens.check(x.shape[0], x.shape[1], x.device):
+        return None
+    if not FUSED_ENCODER:
+        raise ValueError(f"{what}: lens needs the fused encoder kernels (ops.FUSED_ENCODER is False)")
+    if x.shape[-1] % 4 != 0 or x.numel() >= 1 << 31 or any(
+            t is not None and t.data_ptr() % 16 != 0 for t in (x,) + ps):
+        raise ValueError(f"{what}: lens needs C % 4 == 0, 16-byte aligned tensors and fewer than 2^31 elements, "
+                         f"got {tuple(x.shape)}")
+    return lens
 
 
 class AttentionFn(torch.autograd.Function):
@@ -1487,7 +1553,36 @@ class Act(torch.autograd.Function):
         return dx, None
 
 
-def act(x, name):
+class ActLens(torch.autograd.Function):
+    """Act on (B, T, C) with per-sample lengths: rows at or past a sample's length are zeros both ways."""
+
+    @staticmethod
+    def forward(ctx, x, act, lens):
+        B, T, C = x.shape
+        y = _E(x.shape, device=x.device)
+        lib.call("asrx_act_lens_fwd", _P(x), _P(y), _P(lens.table), B, T, C, ACT[act], _S())
+        ctx.act, ctx.lens = act, lens
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        g = _aligned(g)
+        B, T, C = x.shape
+        dx = _E(x.shape, device=x.device)
+        lib.call("asrx_act_lens_bwd", _P(g), _P(x), _P(dx), _P(ctx.lens.table), B, T, C, ACT[ctx.act], _S())
+        return dx, None, None
+
+
+def act(x, name, lens=None):
+    """act(x).  lens (seq_lens, x (B, T, C)): live rows as without it, rows at or past a sample's length are
+    zeros in the output and in the input gradient, whatever x and the incoming gradient hold there."""
+    if lens is not None:
+        x = _c(x)
+        lens = _live_lens(lens, x, "act")
+        if lens is not None:
+            return ActLens.apply(x, name, lens)
     return Act.apply(x, name)
 
 
@@ -1603,11 +1698,40 @@ def _vec4_ok(*ts):
     return all(t is None or (t.data_ptr() % 16 == 0) for t in ts) and ts[0].shape[-1] % 4 == 0
 
 
-def act_dropout(z, act, sid_base, key, p, act2="none"):
+class ActDropoutLens(torch.autograd.Function):
+    """ActDropout with per-sample lengths: rows at or past a sample's length are zeros both ways."""
+
+    @staticmethod
+    def forward(ctx, z, act, sid_base, key, p, act2, lens):
+        B, T, C = z.shape
+        y = _E(z.shape, device=z.device)
+        lib.call("asrx_act_dropout_lens_fwd", _P(z), None, _P(y), _P(lens.table), B, T, C, sid_base,
+                 key & 0xFFFFFFFF, float(p), ACT[act], ACT[act2], _S())
+        ctx.args = (act, sid_base, key, p, act2, lens)
+        ctx.save_for_backward(z)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        act, sid_base, key, p, act2, lens = ctx.args
+        (z,) = ctx.saved_tensors
+        g = _aligned(g)
+        B, T, C = z.shape
+        dz = _E(z.shape, device=z.device)
+        lib.call("asrx_act_dropout_lens_bwd", _P(g), _P(z), _P(dz), _P(lens.table), B, T, C, sid_base,
+                 key & 0xFFFFFFFF, float(p), ACT[act], ACT[act2], _S())
+        return dz, None, None, None, None, None, None
+
+
+def act_dropout(z, act, sid_base, key, p, act2="none", lens=None):
     """act -> Dropout(p) -> act2 on (B, T, C): one fused float4 kernel each way, or the separate ops
-    (bit-identical) when C % 4 != 0 or a tensor is not 16-byte aligned."""
+    (bit-identical) when C % 4 != 0 or a tensor is not 16-byte aligned.  lens (seq_lens): as for act(); the
+    mask index does not depend on T, so the live rows are those of the sample alone with its own sid."""
     z = _c(z)
     _noise_rows_ok(sid_base + z.shape[0], z.shape[2], z.shape[1])
+    lens = _live_lens(lens, z, "act_dropout")
+    if lens is not None:
+        return ActDropoutLens.apply(z, act, sid_base, key, p, act2, lens)
     if _vec4_ok(z):
         return ActDropout.apply(z, act, sid_base, key, p, act2)
     y = Dropout.apply(Act.apply(z, act) if act != "none" else z, sid_base, key, p)
@@ -1745,23 +1869,77 @@ class PreDWConv(torch.autograd.Function):
         return dz, _gret(w, dw, ctx.dw), _gret(b, db, ctx.db), None
 
 
+class PreDWConvLens(torch.autograd.Function):
+    """PreDWConv with per-sample lengths (seq_lens): the conv's taps stop at each sample's length as they stop at
+    T, output rows and input-gradient rows at or past it are zeros, and the weight gradient sums live rows only.
+    pre's forward still runs on every row (row-local; its dead rows are never read)."""
+
+    @staticmethod
+    def forward(ctx, z, w, b, pre, lens):
+        B, T = z.shape[:2]
+        C, K = w.shape[0], w.shape[-1]
+        if z.shape[-1] != (2 * C if pre == "glu" else C):
+            raise ValueError(f"PreDWConv({pre}): input {tuple(z.shape)} does not match {C} conv channels")
+        x = _E(B, T, C, device=z.device)
+        if pre == "glu":
+            lib.call("asrx_glu_fwd", _P(z), _P(x), B * T, C, _S())
+        else:
+            lib.call("asrx_act_fwd", _P(z), _P(x), x.numel(), ACT[pre], _S())
+        y = _E(B, T, C, device=z.device)
+        lib.call("asrx_dwconv_lens_fwd", _P(x), _P(w), _P(b), _P(y), _P(lens.table), B, T, C, K, _S())
+        ctx.pre, ctx.lens = pre, lens
+        ctx.dw, ctx.db = _direct(ctx, 1, w), _direct(ctx, 2, b)
+        ctx.save_for_backward(z, x, w, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        z, x, w, b = ctx.saved_tensors
+        g = _aligned(g)
+        B, T, C = x.shape
+        K = w.shape[-1]
+        dz = _E(z.shape, device=z.device)
+        dw, db = _gbuf(w, ctx.dw), _gbuf(b, ctx.db)
+        lib.call("asrx_dwconv_pre_lens_bwd", _P(g), _P(x), _P(z), _P(w), _P(dz), _P(dw), _P(db), _P(ctx.lens.table),
+                 B, T, C, K, DW_PRE[ctx.pre], _S())
+        return dz, _gret(w, dw, ctx.dw), _gret(b, db, ctx.db), None, None
+
+
 def _pre_dwconv(z, w, pre):
     C, K = w.shape[0], w.shape[-1]
     return (FUSED_ENCODER and K == _DW_PRE_K[pre] and C % 4 == 0 and z.numel() < 1 << 31
             and z.data_ptr() % 16 == 0)
 
 
-def glu_dwconv(x, w, b):
-    """DWConv(GLU(x)) for x (B, T, 2C)."""
+def _pre_dwconv_lens(z, w, b, pre, lens, what):
+    lens = _live_lens(lens, z, what, b)
+    if lens is not None and (w.shape[-1] != _DW_PRE_K[pre] or w.shape[0] % 4 != 0):
+        raise ValueError(f"{what}: lens needs the fused {pre} -> k{_DW_PRE_K[pre]} form with C % 4 == 0, got a "
+                         f"weight {tuple(w.shape)}")
+    return lens
+
+
+def glu_dwconv(x, w, b, lens=None):
+    """DWConv(GLU(x)) for x (B, T, 2C).  lens (seq_lens): sample b's rows [0, T_b) as for x[b:b+1, :T_b] alone,
+    zeros past them (output and input gradient); nothing live depends on the pad rows of x or of the gradient."""
     x = _c(x)
+    lens = _pre_dwconv_lens(x, w, b, "glu", lens, "glu_dwconv")
+    if lens is not None:
+        return PreDWConvLens.apply(x, w, b, "glu", lens)
     if _pre_dwconv(x, w, "glu"):
         return PreDWConv.apply(x, w, b, "glu")
     return DWConv.apply(glu(x), w, b)
 
 
-def act_dwconv(x, name, w, b):
-    """DWConv(act(x))."""
+def act_dwconv(x, name, w, b, lens=None):
+    """DWConv(act(x)).  lens (seq_lens, gelu -> k3 only): as for glu_dwconv."""
     x = _c(x)
+    if lens is not None:
+        if name != "gelu":
+            raise ValueError(f"act_dwconv: lens needs the fused gelu -> k3 form, got {name!r}")
+        lens = _pre_dwconv_lens(x, w, b, "gelu", lens, "act_dwconv")
+        if lens is not None:
+            return PreDWConvLens.apply(x, w, b, "gelu", lens)
     if name == "gelu" and _pre_dwconv(x, w, "gelu"):
         return PreDWConv.apply(x, w, b, "gelu")
     return DWConv.apply(act(x, name), w, b)
@@ -1804,9 +1982,46 @@ def _bn_silu_ok(x, *ps):
             and all(t.data_ptr() % 16 == 0 for t in (x,) + ps))
 
 
-def batch_norm_silu(x, w, b, eps, stats):
-    """silu(BatchNormPS(x)) in train mode."""
+class BatchNormSiLULens(torch.autograd.Function):
+    """BatchNormSiLU with per-sample lengths (seq_lens): each sample's statistics over its live rows; output and
+    input-gradient rows at or past its length are zeros."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, eps, stats, lens):
+        B, T, C = x.shape
+        mean = _E(B, C, device=x.device)
+        rstd = _E(B, C, device=x.device)
+        y = _E(x.shape, device=x.device)
+        lib.call("asrx_bn_silu_lens_fwd", _P(x), _P(w), _P(b), _P(y), _P(mean), _P(rstd), _P(lens.table), B, T, C,
+                 float(eps), 1, _S())
+        if stats is not None:
+            stats.append((mean, rstd))
+        ctx.lens = lens
+        ctx.dw, ctx.db = _direct(ctx, 1, w), _direct(ctx, 2, b)
+        ctx.save_for_backward(x, w, mean, rstd, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, mean, rstd, b = ctx.saved_tensors
+        g = _aligned(g)
+        B, T, C = x.shape
+        sg = _E(B, C, device=x.device)
+        sgx = _E(B, C, device=x.device)
+        dx = _E(x.shape, device=x.device)
+        dw, db = _gbuf(w, ctx.dw), _gbuf(b, ctx.db)
+        lib.call("asrx_bn_silu_lens_bwd", _P(g), _P(x), _P(mean), _P(rstd), _P(w), _P(b), _P(sg), _P(sgx), _P(dx),
+                 _P(dw), _P(db), _P(ctx.lens.table), B, T, C, _S())
+        return dx, _gret(w, dw, ctx.dw), _gret(b, db, ctx.db), None, None, None
+
+
+def batch_norm_silu(x, w, b, eps, stats, lens=None):
+    """silu(BatchNormPS(x)) in train mode.  lens (seq_lens): the statistics of sample b over its rows [0, T_b),
+    those rows as for x[b:b+1, :T_b] alone, zeros past them (output and input gradient)."""
     x = _c(x)
+    lens = _live_lens(lens, x, "batch_norm_silu", w, b)
+    if lens is not None:
+        return BatchNormSiLULens.apply(x, w, b, eps, stats, lens)
     if _bn_silu_ok(x, w, b):
         return BatchNormSiLU.apply(x, w, b, eps, stats)
     return act(BatchNormPS.apply(x, w, b, eps, stats), "silu")

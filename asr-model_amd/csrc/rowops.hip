@@ -1453,12 +1453,33 @@ __global__ void lincomb4_kernel(const float4* __restrict__ x, const float4* __re
   }
   if (i < n4) out[i] = one(x[i], y ? y[i] : zero, z ? z[i] : zero);
 }
-__global__ void act_fwd4_kernel(const float4* __restrict__ x, float4* __restrict__ y, uint32_t n4, int act) {
+// Per-sample lengths (the LENS instantiations of the encoder's row-crossing kernels below): sample b's live
+// row count T_b of the (B,) int32 device table, clamped to the launch extent T so that a bad table cannot
+// address past it.  T keeps the grid and the addressing; T_b takes its place as the row limit: rows at or past
+// it count as zeros on the way in (never loaded) and are stored as zeros on the way out (a select, so what
+// they held, NaN included, reaches nothing).  Live values are formed by the expressions and in the order of
+// the uniform instantiation run on x[b, :T_b] alone.
+__device__ __forceinline__ int seq_len(const int32_t* __restrict__ lens, int64_t b, int T) {
+  return min(max(lens[b], 0), T);
+}
+
+template <bool LENS = false>
+__global__ void act_fwd4_kernel(const float4* __restrict__ x, float4* __restrict__ y, uint32_t n4, int act,
+                                uint32_t C4, uint32_t T, const int32_t* __restrict__ lens) {
   const uint32_t st = gridDim.x * blockDim.x;
   auto one = [&](float4 v) __attribute__((always_inline)) {
     return make_float4(apply_act(act, v.x), apply_act(act, v.y), apply_act(act, v.z), apply_act(act, v.w));
   };
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (LENS) {  // y = live ? act(x) : 0, dead rows not loaded
+    for (; i < n4; i += st) {
+      const uint32_t row = i / C4, b = row / T, t = row - b * T;
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+      if ((int)t < seq_len(lens, b, (int)T)) o = one(x[i]);
+      y[i] = o;
+    }
+    return;
+  }
   for (; i + st < n4; i += 2 * st) {
     const float4 a0 = x[i], a1 = x[i + st];
     y[i] = one(a0);
@@ -1478,14 +1499,24 @@ __device__ __forceinline__ float act_deriv(int act, float v) {
     default: return 1.f;
   }
 }
+template <bool LENS = false>
 __global__ void act_bwd4_kernel(const float4* __restrict__ g, const float4* __restrict__ x, float4* __restrict__ dx,
-                                uint32_t n4, int act) {
+                                uint32_t n4, int act, uint32_t C4, uint32_t T, const int32_t* __restrict__ lens) {
   const uint32_t st = gridDim.x * blockDim.x;
   auto one = [&](float4 gv, float4 v) __attribute__((always_inline)) {
     return make_float4(gv.x * act_deriv(act, v.x), gv.y * act_deriv(act, v.y), gv.z * act_deriv(act, v.z),
                        gv.w * act_deriv(act, v.w));
   };
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (LENS) {  // dx = live ? g act'(x) : 0, dead rows of g and x not loaded
+    for (; i < n4; i += st) {
+      const uint32_t row = i / C4, b = row / T, t = row - b * T;
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+      if ((int)t < seq_len(lens, b, (int)T)) o = one(g[i], x[i]);
+      dx[i] = o;
+    }
+    return;
+  }
   for (; i + st < n4; i += 2 * st) {
     const float4 g0 = g[i], g1 = g[i + st], v0 = x[i], v1 = x[i + st];
     dx[i] = one(g0, v0);
@@ -1623,17 +1654,24 @@ __device__ __forceinline__ float act_grad(int act, float v) {
 // when the layer output has no other consumer; the backward recomputes act(z) for act2'.
 // res (forward only, nullable) adds a residual after everything: ConvLite's `res + dropout(point2(.))`
 // (model.py:107-118) in the same pass.
-template <bool BWD>
+// LENS (seq_len above): a row at or past its sample's length stores zeros, residual included, and loads nothing.
+template <bool BWD, bool LENS = false>
 __global__ void act_dropout4_kernel(const float4* __restrict__ g, const float4* __restrict__ z,
                                     const float4* __restrict__ res, float4* __restrict__ out, uint32_t n4,
                                     uint32_t C4, uint32_t T, uint32_t C, uint32_t sid_base, uint32_t key, float p,
-                                    int act, int act2) {
+                                    int act, int act2, const int32_t* __restrict__ lens) {
   const float sc = 1.0f / (1.0f - p);
   key = noise_key(key);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
     const uint32_t row = i / C4, c0 = (i - row * C4) * 4u;
     const uint32_t t = row % T, b = row / T;
     const uint32_t base = ((sid_base + b) * C + c0) * 8192u + t;
+    if constexpr (LENS) {
+      if ((int)t >= seq_len(lens, b, (int)T)) {
+        out[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+    }
     const float4 v = z[i];
     float r[4] = {v.x, v.y, v.z, v.w};
     float gg[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1756,11 +1794,16 @@ __global__ __launch_bounds__(256) void dwconv_bwd_w_kernel(const float* __restri
 constexpr int DW_R = 16;
 enum { DW_PRE_NONE = 0, DW_PRE_GLU = 1, DW_PRE_GELU = 2 };
 
-template <int K, bool FLIP, int PRE = DW_PRE_NONE>
+//
+// LENS (seq_len above; the table load is per thread, a 256-thread block can span samples): input rows at or past
+// T_b count as zeros like the rows past T, output rows [T_b, T) are stored as zeros (z is not read there), and
+// a tile that starts at or past T_b stores its zeros and returns before the weight loads.
+template <int K, bool FLIP, int PRE = DW_PRE_NONE, bool LENS = false>
 __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restrict__ x, const float* __restrict__ w,
                                                           const float* __restrict__ b, float4* __restrict__ y,
                                                           int B, int T, int C4, int ntile,
-                                                          const float4* __restrict__ z) {
+                                                          const float4* __restrict__ z,
+                                                          const int32_t* __restrict__ lens) {
   constexpr int P = K / 2, W = DW_R + K - 1;
   static_assert(FLIP || PRE == DW_PRE_NONE, "PRE is an epilogue of the data-gradient form");
   const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1770,6 +1813,22 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
   const int t0 = (int)(rest % ntile) * DW_R;
   const int64_t bb = rest / ntile;
   const float4* xs = x + bb * T * C4 + c4;
+  int Tb = T;  // the row limit of loads and of live outputs
+  if constexpr (LENS) {
+    Tb = seq_len(lens, bb, T);
+    if (t0 >= Tb) {  // a dead tile: zeros, nothing loaded
+      constexpr int YW = PRE == DW_PRE_GLU ? 2 : 1;  // the GLU form writes 2C-wide rows
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      float4* ys = y + bb * T * YW * C4 + c4;
+#pragma unroll
+      for (int r = 0; r < DW_R; ++r)
+        if (t0 + r < T) {
+          ys[(int64_t)(t0 + r) * YW * C4] = zero;
+          if constexpr (YW == 2) ys[(int64_t)(t0 + r) * YW * C4 + C4] = zero;
+        }
+      return;
+    }
+  }
   float4 wk[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -1786,7 +1845,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
   for (int j = 0; j < W; ++j) {
     const int row = t0 - P + j;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row >= 0 && row < T) v = xs[(int64_t)row * C4];
+    if (row >= 0 && row < Tb) v = xs[(int64_t)row * C4];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int r = j - k;
@@ -1803,7 +1862,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
     float4* ys = y + bb * T * 2 * C4 + c4;
 #pragma unroll
     for (int r = 0; r < DW_R; ++r)
-      if (t0 + r < T) {
+      if (t0 + r < Tb) {
         const int64_t o = (int64_t)(t0 + r) * 2 * C4;
         const float4 a = zs[o], q = zs[o + C4], g = acc[r];
         const float sx = sigmoid_f(q.x), sy = sigmoid_f(q.y), sz = sigmoid_f(q.z), sw = sigmoid_f(q.w);
@@ -1816,7 +1875,7 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
     float4* ys = y + bb * T * C4 + c4;
 #pragma unroll
     for (int r = 0; r < DW_R; ++r)
-      if (t0 + r < T) {
+      if (t0 + r < Tb) {
         const float4 v = zs[(int64_t)(t0 + r) * C4], g = acc[r];
         ys[(int64_t)(t0 + r) * C4] =
             make_float4(g.x * gelu_grad(v.x), g.y * gelu_grad(v.y), g.z * gelu_grad(v.z), g.w * gelu_grad(v.w));
@@ -1825,7 +1884,17 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
     float4* ys = y + bb * T * C4 + c4;
 #pragma unroll
     for (int r = 0; r < DW_R; ++r)
-      if (t0 + r < T) ys[(int64_t)(t0 + r) * C4] = acc[r];
+      if (t0 + r < Tb) ys[(int64_t)(t0 + r) * C4] = acc[r];
+  }
+  if constexpr (LENS) {  // the dead rows of a half-live tile: zeros, after the live rows' epilogue (as without LENS)
+    constexpr int YW = PRE == DW_PRE_GLU ? 2 : 1;
+    float4* ys = y + bb * T * YW * C4 + c4;
+#pragma unroll
+    for (int r = 1; r < DW_R; ++r)
+      if (t0 + r >= Tb && t0 + r < T) {
+        ys[(int64_t)(t0 + r) * YW * C4] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (YW == 2) ys[(int64_t)(t0 + r) * YW * C4 + C4] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
   }
 }
 
@@ -1836,10 +1905,11 @@ __global__ __launch_bounds__(256) void dwconv_tile_kernel(const float4* __restri
 // -- leave as coalesced atomics.
 constexpr int DW_S = 4;
 
-template <int K>
+// LENS (seq_len above): g and x rows are limited by the sample's T_b; a chunk at or past it adds nothing.
+template <int K, bool LENS = false>
 __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float4* __restrict__ g, const float4* __restrict__ x,
                                                            float* __restrict__ dw, float* __restrict__ db, int T,
-                                                           int C4, int nchunk) {
+                                                           int C4, int nchunk, const int32_t* __restrict__ lens) {
   constexpr int P = K / 2, W = DW_R + K - 1;
   __shared__ float4 red[4][32][K + 1];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1849,6 +1919,11 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float4* __restr
   const int chunk = (blockIdx.x / cchunks) % nchunk;
   const int64_t bb = blockIdx.x / ((int64_t)cchunks * nchunk);
   const int c4 = cc * 32 + cl;
+  int Tb = T;  // the row limit (the addressing keeps T)
+  if constexpr (LENS) {
+    Tb = seq_len(lens, bb, T);
+    if (chunk * (8 * DW_S * DW_R) >= Tb) return;  // workgroup-uniform: no live row in this chunk
+  }
   float4 acc[K + 1];
 #pragma unroll
   for (int k = 0; k <= K; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1857,18 +1932,18 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float4* __restr
     const float4* xs = x + bb * T * C4 + c4;
     for (int s = 0; s < DW_S; ++s) {
       const int t0 = ((chunk * 8 + grp) * DW_S + s) * DW_R;
-      if (t0 >= T) break;
+      if (t0 >= Tb) break;
       float4 gv[DW_R];
 #pragma unroll
       for (int r = 0; r < DW_R; ++r) {
-        gv[r] = (t0 + r < T) ? gs[(int64_t)(t0 + r) * C4] : make_float4(0.f, 0.f, 0.f, 0.f);
+        gv[r] = (t0 + r < Tb) ? gs[(int64_t)(t0 + r) * C4] : make_float4(0.f, 0.f, 0.f, 0.f);
         acc[K].x += gv[r].x; acc[K].y += gv[r].y; acc[K].z += gv[r].z; acc[K].w += gv[r].w;
       }
 #pragma unroll
       for (int j = 0; j < W; ++j) {
         const int row = t0 - P + j;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row >= 0 && row < T) v = xs[(int64_t)row * C4];
+        if (row >= 0 && row < Tb) v = xs[(int64_t)row * C4];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
           const int r = j - k;
@@ -1916,15 +1991,26 @@ static void dwconv_tiled(const float* x, const float* w, const float* b, float* 
   const int64_t threads = B * ntile * C4;
   const unsigned grid = (unsigned)((threads + 255) / 256);
   if (y) dwconv_tile_kernel<K, false><<<grid, 256, 0, stream>>>((const float4*)x, w, b, (float4*)y, (int)B, (int)T, C4,
-                                                                 ntile, nullptr);
+                                                                 ntile, nullptr, nullptr);
   if (dx) dwconv_tile_kernel<K, true><<<grid, 256, 0, stream>>>((const float4*)g, w, nullptr, (float4*)dx, (int)B,
-                                                                 (int)T, C4, ntile, nullptr);
+                                                                 (int)T, C4, ntile, nullptr, nullptr);
   if (dw) {
     const int nchunk = (int)((T + 8 * DW_S * DW_R - 1) / (8 * DW_S * DW_R));
     const int64_t blocks = B * nchunk * ((C4 + 31) / 32);
     dwconv_wgrad_kernel<K><<<(unsigned)blocks, 256, 0, stream>>>((const float4*)g, (const float4*)x, dw, db, (int)T,
-                                                                   C4, nchunk);
+                                                                   C4, nchunk, nullptr);
   }
+}
+
+// Forward with per-sample lengths (asrx_dwconv_lens_fwd): the LENS instantiation on dwconv_tiled's grid.
+template <int K>
+static void dwconv_tiled_lens_fwd(const float* x, const float* w, const float* b, float* y, const int32_t* lens,
+                                  int64_t B, int64_t T, int64_t C, hipStream_t stream) {
+  const int C4 = (int)(C / 4);
+  const int ntile = (int)((T + DW_R - 1) / DW_R);
+  const int64_t threads = B * ntile * C4;
+  dwconv_tile_kernel<K, false, DW_PRE_NONE, true><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+      (const float4*)x, w, b, (float4*)y, (int)B, (int)T, C4, ntile, nullptr, lens);
 }
 
 // Backward of op -> conv in two launches (PRE, see dwconv_tile_kernel): the data-gradient kernel
@@ -1939,19 +2025,20 @@ static bool dwconv_pre_ok(const float* g, const float* x, const float* z, const 
   return form && C % 4 == 0 && (al & 15) == 0 && B * T * C * (pre == DW_PRE_GLU ? 2 : 1) < (1LL << 31);
 }
 
-template <int K, int PRE>
+template <int K, int PRE, bool LENS = false>
 static void dwconv_pre_bwd_launch(const float* g, const float* x, const float* z, const float* w, float* dz, float* dw,
-                                  float* db, int64_t B, int64_t T, int64_t C, hipStream_t stream) {
+                                  float* db, int64_t B, int64_t T, int64_t C, hipStream_t stream,
+                                  const int32_t* lens = nullptr) {
   const int C4 = (int)(C / 4);
   const int ntile = (int)((T + DW_R - 1) / DW_R);
   const int64_t threads = B * ntile * C4;
-  dwconv_tile_kernel<K, true, PRE><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
-      (const float4*)g, w, nullptr, (float4*)dz, (int)B, (int)T, C4, ntile, (const float4*)z);
+  dwconv_tile_kernel<K, true, PRE, LENS><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(
+      (const float4*)g, w, nullptr, (float4*)dz, (int)B, (int)T, C4, ntile, (const float4*)z, lens);
   if (dw) {
     const int nchunk = (int)((T + 8 * DW_S * DW_R - 1) / (8 * DW_S * DW_R));
     const int64_t blocks = B * nchunk * ((C4 + 31) / 32);
-    dwconv_wgrad_kernel<K><<<(unsigned)blocks, 256, 0, stream>>>((const float4*)g, (const float4*)x, dw, db, (int)T,
-                                                                   C4, nchunk);
+    dwconv_wgrad_kernel<K, LENS><<<(unsigned)blocks, 256, 0, stream>>>((const float4*)g, (const float4*)x, dw, db,
+                                                                         (int)T, C4, nchunk, lens);
   }
 }
 
@@ -2017,18 +2104,26 @@ __device__ __forceinline__ void chan_combine(float& na, float& ma, float& m2a, f
   na = n;
 }
 
+//
+// LENS (seq_len above): the statistics of rows [0, T_b) -- the row loop, the row-group counts and the divisor use
+// T_b; the 32 row groups still start at rows 0..31, so the Welford / Chan order is that of the sample alone.
+// T_b = 0 writes mean 0 and rstd 0.
+template <bool LENS = false>
 __global__ __launch_bounds__(1024) void bn_stats4_kernel(const float4* __restrict__ x, float* __restrict__ mean,
-                                                         float* __restrict__ rstd, int T, int C4, float eps) {
+                                                         float* __restrict__ rstd, int Tx, int C4, float eps,
+                                                         const int32_t* __restrict__ lens) {
   __shared__ float4 sm[32][32], sq[32][32];
   const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int cchunks = (C4 + 31) / 32;
   const int cc = blockIdx.x % cchunks;
   const int64_t b = blockIdx.x / cchunks;
   const int c4 = cc * 32 + lane;
+  int T = Tx;  // the row limit; Tx keeps the addressing
+  if constexpr (LENS) T = seq_len(lens, b, Tx);
   float4 mu = make_float4(0.f, 0.f, 0.f, 0.f), m2 = mu;
   float n = 0.f;
   if (c4 < C4) {
-    const float4* xs = x + b * T * C4 + c4;
+    const float4* xs = x + b * Tx * C4 + c4;
     for (int t = grp; t < T; t += 32) {
       const float4 v = xs[(int64_t)t * C4];
       n += 1.f;
@@ -2060,6 +2155,10 @@ __global__ __launch_bounds__(1024) void bn_stats4_kernel(const float4* __restric
     float* mo = mean + b * 4 * C4 + 4 * c4;
     float* ro = rstd + b * 4 * C4 + 4 * c4;
     mo[0] = ma.x; mo[1] = ma.y; mo[2] = ma.z; mo[3] = ma.w;
+    if (LENS && T == 0) {
+      ro[0] = ro[1] = ro[2] = ro[3] = 0.f;
+      return;
+    }
     ro[0] = rsqrtf(qa.x / T + eps); ro[1] = rsqrtf(qa.y / T + eps);
     ro[2] = rsqrtf(qa.z / T + eps); ro[3] = rsqrtf(qa.w / T + eps);
   }
@@ -2069,26 +2168,30 @@ __global__ __launch_bounds__(1024) void bn_stats4_kernel(const float4* __restric
 // SILU: g is the gradient of silu(BatchNorm(x)); the BatchNorm output is recomputed from x and the
 // statistics (bn_apply_kernel's expression) and g * silu'(.) formed in registers (act_bwd4_kernel's
 // product), then summed in the same row-group loop and order -- the same sums as on a stored product.
-template <bool SILU = false>
+// LENS (seq_len above): the sums run over rows below T_b only.
+template <bool SILU = false, bool LENS = false>
 __global__ __launch_bounds__(1024) void bn_bwd_stats4_kernel(const float4* __restrict__ g, const float4* __restrict__ x,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
                                                              const float* __restrict__ w, float* __restrict__ sg,
                                                              float* __restrict__ sgx, float* __restrict__ dw,
-                                                             float* __restrict__ db, int T, int C4,
-                                                             const float* __restrict__ bias) {
+                                                             float* __restrict__ db, int Tx, int C4,
+                                                             const float* __restrict__ bias,
+                                                             const int32_t* __restrict__ lens) {
   __shared__ float4 sa[32][32], sx[32][32];
   const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
   const int cchunks = (C4 + 31) / 32;
   const int cc = blockIdx.x % cchunks;
   const int64_t b = blockIdx.x / cchunks;
   const int c4 = cc * 32 + lane;
+  int T = Tx;  // the row limit; Tx keeps the addressing
+  if constexpr (LENS) T = seq_len(lens, b, Tx);
   float4 a = make_float4(0.f, 0.f, 0.f, 0.f), ax = a;
   if (c4 < C4) {
     const float4 mu = *reinterpret_cast<const float4*>(mean + b * 4 * C4 + 4 * c4);
     const float4 rs = *reinterpret_cast<const float4*>(rstd + b * 4 * C4 + 4 * c4);
-    const float4* gs = g + b * T * C4 + c4;
-    const float4* xs = x + b * T * C4 + c4;
+    const float4* gs = g + b * Tx * C4 + c4;
+    const float4* xs = x + b * Tx * C4 + c4;
     float4 wv = make_float4(0.f, 0.f, 0.f, 0.f), bv = wv;
     if constexpr (SILU) {
       wv = *reinterpret_cast<const float4*>(w + 4 * c4);
@@ -2201,13 +2304,23 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __
 // is never stored.  Requires C % 4 == 0, 16-byte alignment (statistics and parameters included) and
 // n / 4 < 2^31.
 //   fwd: y = silu((x - mean) * rstd * w + bb)   (mean / rstd per sample, or shared when !per_sample: eval)
+// LENS (seq_len above), both ways: a row at or past its sample's length stores zeros and loads nothing; the
+// backward divides by T_b.
+template <bool LENS = false>
 __global__ void bn_silu_apply4_kernel(const float4* __restrict__ x, const float* __restrict__ mean,
                                       const float* __restrict__ rstd, const float* __restrict__ w,
                                       const float* __restrict__ bb, float4* __restrict__ y, uint32_t n4, uint32_t C4,
-                                      uint32_t T, int per_sample) {
+                                      uint32_t T, int per_sample, const int32_t* __restrict__ lens) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
     const uint32_t row = i / C4, c0 = (i - row * C4) * 4u;
     const uint32_t s = per_sample ? (row / T) * (C4 * 4u) + c0 : c0;
+    if constexpr (LENS) {
+      const uint32_t b = row / T;
+      if ((int)(row - b * T) >= seq_len(lens, b, (int)T)) {
+        y[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+    }
     const float4 v = x[i];
     const float4 mu = *reinterpret_cast<const float4*>(mean + s), rs = *reinterpret_cast<const float4*>(rstd + s);
     const float4 wv = *reinterpret_cast<const float4*>(w + c0), bv = *reinterpret_cast<const float4*>(bb + c0);
@@ -2217,12 +2330,14 @@ __global__ void bn_silu_apply4_kernel(const float4* __restrict__ x, const float*
 }
 
 //   bwd: gz = g * silu'(BatchNorm(x)) recomputed, then bn_bwd_apply_kernel's expression on gz
+template <bool LENS = false>
 __global__ void bn_silu_bwd_apply4_kernel(const float4* __restrict__ g, const float4* __restrict__ x,
                                           const float* __restrict__ mean, const float* __restrict__ rstd,
                                           const float* __restrict__ w, const float* __restrict__ bb,
                                           const float* __restrict__ sg, const float* __restrict__ sgx,
-                                          float4* __restrict__ dx, uint32_t n4, uint32_t C4, uint32_t T) {
-  const float Tf = (float)T;
+                                          float4* __restrict__ dx, uint32_t n4, uint32_t C4, uint32_t T,
+                                          const int32_t* __restrict__ lens) {
+  float Tf = (float)T;
   auto one = [&](float gv, float xv, float mu, float rs, float wc, float bc, float sgs, float sgxs)
                  __attribute__((always_inline)) {
     const float xh = (xv - mu) * rs;
@@ -2232,6 +2347,15 @@ __global__ void bn_silu_bwd_apply4_kernel(const float4* __restrict__ g, const fl
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
     const uint32_t row = i / C4, c0 = (i - row * C4) * 4u;
     const uint32_t s = (row / T) * (C4 * 4u) + c0;
+    if constexpr (LENS) {
+      const uint32_t b = row / T;
+      const int Tb = seq_len(lens, b, (int)T);
+      if ((int)(row - b * T) >= Tb) {
+        dx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+      Tf = (float)Tb;
+    }
     const float4 gv = g[i], xv = x[i];
     const float4 mu = *reinterpret_cast<const float4*>(mean + s), rs = *reinterpret_cast<const float4*>(rstd + s);
     const float4 wv = *reinterpret_cast<const float4*>(w + c0), bv = *reinterpret_cast<const float4*>(bb + c0);
@@ -3050,11 +3174,52 @@ int asrx_act_fwd(const float* x, float* y, int64_t n, int act, hipStream_t strea
   if (n == 0) return 0;
   if (n % 4 == 0 && n / 4 < (1LL << 31) && ((((uintptr_t)x | (uintptr_t)y) & 15) == 0)) {
     const int64_t n4 = n / 4;
-    act_fwd4_kernel<<<ew_grid((n4 + 1) / 2, 8192), 256, 0, stream>>>((const float4*)x, (float4*)y, (uint32_t)n4, act);
+    act_fwd4_kernel<<<ew_grid((n4 + 1) / 2, 8192), 256, 0, stream>>>((const float4*)x, (float4*)y, (uint32_t)n4, act,
+                                                                     0u, 0u, nullptr);
   } else {
     LAUNCH_EW(act_fwd_kernel, n, x, y, n, act);
   }
   ASRX_LAUNCHED("asrx_act_fwd");
+}
+
+// ---- per-sample lengths (seq_len): the LENS instantiations.  Each entry point takes its uniform twin's
+// arguments plus `lens` (B int32 on the device) ahead of the sizes, keeps the twin's early return and refusals in
+// place and words, refuses what only the twin's non-float4 fall-back would take, then a null and a misaligned
+// table; every check answers before anything is launched.
+#define ASRX_REQUIRE_LENS(name)                                                                 \
+  ASRX_REQUIRE(lens != nullptr, name ": per-sample lengths: null table");                       \
+  ASRX_REQUIRE(((uintptr_t)lens & 3) == 0, name ": per-sample lengths: table must be 4-byte aligned")
+
+static bool lens_vec_ok(std::initializer_list<const void*> ps, int64_t B, int64_t T, int64_t C) {
+  uintptr_t al = 0;
+  for (const void* p : ps) al |= (uintptr_t)p;
+  return C % 4 == 0 && (al & 15) == 0 && B * T * C < (1LL << 31);
+}
+
+// asrx_act_fwd on (B, T, C): y = live ? act(x) : 0
+int asrx_act_lens_fwd(const float* x, float* y, const int32_t* lens, int64_t B, int64_t T, int64_t C, int act,
+                      hipStream_t stream) {
+  if (B * T * C == 0) return 0;
+  ASRX_REQUIRE(lens_vec_ok({x, y}, B, T, C),
+               "asrx_act_lens_fwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
+  ASRX_REQUIRE_LENS("asrx_act_lens_fwd");
+  const int64_t n4 = B * T * C / 4;
+  act_fwd4_kernel<true><<<ew_grid(n4, 8192), 256, 0, stream>>>((const float4*)x, (float4*)y, (uint32_t)n4, act,
+                                                               (uint32_t)(C / 4), (uint32_t)T, lens);
+  ASRX_LAUNCHED("asrx_act_lens_fwd");
+}
+
+// asrx_act_bwd on (B, T, C): dx = live ? g act'(x) : 0
+int asrx_act_lens_bwd(const float* g, const float* x, float* dx, const int32_t* lens, int64_t B, int64_t T, int64_t C,
+                      int act, hipStream_t stream) {
+  if (B * T * C == 0) return 0;
+  ASRX_REQUIRE(lens_vec_ok({g, x, dx}, B, T, C),
+               "asrx_act_lens_bwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
+  ASRX_REQUIRE_LENS("asrx_act_lens_bwd");
+  const int64_t n4 = B * T * C / 4;
+  act_bwd4_kernel<true><<<ew_grid(n4, 8192), 256, 0, stream>>>((const float4*)g, (const float4*)x, (float4*)dx,
+                                                               (uint32_t)n4, act, (uint32_t)(C / 4), (uint32_t)T, lens);
+  ASRX_LAUNCHED("asrx_act_lens_bwd");
 }
 
 int asrx_act_bwd(const float* g, const float* x, float* dx, int64_t n, int act, hipStream_t stream) {
@@ -3062,7 +3227,7 @@ int asrx_act_bwd(const float* g, const float* x, float* dx, int64_t n, int act, 
   if (n % 4 == 0 && n / 4 < (1LL << 31) && ((((uintptr_t)g | (uintptr_t)x | (uintptr_t)dx) & 15) == 0)) {
     const int64_t n4 = n / 4;
     act_bwd4_kernel<<<ew_grid((n4 + 1) / 2, 8192), 256, 0, stream>>>((const float4*)g, (const float4*)x, (float4*)dx,
-                                                                     (uint32_t)n4, act);
+                                                                     (uint32_t)n4, act, 0u, 0u, nullptr);
   } else {
     LAUNCH_EW(act_bwd_kernel, n, g, x, dx, n, act);
   }
@@ -3109,7 +3274,7 @@ int asrx_dropout(const float* x, float* y, int64_t B, int64_t T, int64_t C, int6
   if (act_dropout_vec_ok(x, y, nullptr, n, C))
     LAUNCH_EW(act_dropout4_kernel<false>, n / 4, nullptr, reinterpret_cast<const float4*>(x), nullptr,
               reinterpret_cast<float4*>(y), (uint32_t)(n / 4), (uint32_t)(C / 4), (uint32_t)T, (uint32_t)C,
-              (uint32_t)sid_base, key, p, (int)ACT_NONE, (int)ACT_NONE);
+              (uint32_t)sid_base, key, p, (int)ACT_NONE, (int)ACT_NONE, nullptr);
   else
     LAUNCH_EW(dropout_kernel, n, x, y, B, T, (int)C, sid_base, key, p);
   ASRX_LAUNCHED("asrx_dropout");
@@ -3122,7 +3287,7 @@ int asrx_act_dropout_fwd(const float* z, const float* res, float* y, int64_t B, 
   ASRX_REQUIRE(act_dropout_vec_ok(z, y, res, n, C), "act_dropout: needs C %% 4 == 0 and 16-byte aligned tensors");
   LAUNCH_EW(act_dropout4_kernel<false>, n / 4, nullptr, reinterpret_cast<const float4*>(z),
             reinterpret_cast<const float4*>(res), reinterpret_cast<float4*>(y), (uint32_t)(n / 4), (uint32_t)(C / 4), (uint32_t)T, (uint32_t)C,
-            (uint32_t)sid_base, key, p, act, act2);
+            (uint32_t)sid_base, key, p, act, act2, nullptr);
   ASRX_LAUNCHED("asrx_act_dropout_fwd");
 }
 
@@ -3133,8 +3298,35 @@ int asrx_act_dropout_bwd(const float* g, const float* z, float* dz, int64_t B, i
   ASRX_REQUIRE(act_dropout_vec_ok(g, z, dz, n, C), "act_dropout: needs C %% 4 == 0 and 16-byte aligned tensors");
   LAUNCH_EW(act_dropout4_kernel<true>, n / 4, reinterpret_cast<const float4*>(g), reinterpret_cast<const float4*>(z),
             nullptr, reinterpret_cast<float4*>(dz), (uint32_t)(n / 4), (uint32_t)(C / 4), (uint32_t)T, (uint32_t)C,
-            (uint32_t)sid_base, key, p, act, act2);
+            (uint32_t)sid_base, key, p, act, act2, nullptr);
   ASRX_LAUNCHED("asrx_act_dropout_bwd");
+}
+
+// asrx_act_dropout_fwd / _bwd with per-sample lengths: dead rows are zeros (the residual included)
+int asrx_act_dropout_lens_fwd(const float* z, const float* res, float* y, const int32_t* lens, int64_t B, int64_t T,
+                              int64_t C, int64_t sid_base, uint32_t key, float p, int act, int act2,
+                              hipStream_t stream) {
+  const int64_t n = B * T * C;
+  if (n == 0) return 0;
+  ASRX_REQUIRE(act_dropout_vec_ok(z, y, res, n, C), "act_dropout: needs C %% 4 == 0 and 16-byte aligned tensors");
+  ASRX_REQUIRE_LENS("asrx_act_dropout_lens_fwd");
+  act_dropout4_kernel<false, true><<<ew_grid(n / 4), 256, 0, stream>>>(
+      nullptr, reinterpret_cast<const float4*>(z), reinterpret_cast<const float4*>(res), reinterpret_cast<float4*>(y),
+      (uint32_t)(n / 4), (uint32_t)(C / 4), (uint32_t)T, (uint32_t)C, (uint32_t)sid_base, key, p, act, act2, lens);
+  ASRX_LAUNCHED("asrx_act_dropout_lens_fwd");
+}
+
+int asrx_act_dropout_lens_bwd(const float* g, const float* z, float* dz, const int32_t* lens, int64_t B, int64_t T,
+                              int64_t C, int64_t sid_base, uint32_t key, float p, int act, int act2,
+                              hipStream_t stream) {
+  const int64_t n = B * T * C;
+  if (n == 0) return 0;
+  ASRX_REQUIRE(act_dropout_vec_ok(g, z, dz, n, C), "act_dropout: needs C %% 4 == 0 and 16-byte aligned tensors");
+  ASRX_REQUIRE_LENS("asrx_act_dropout_lens_bwd");
+  act_dropout4_kernel<true, true><<<ew_grid(n / 4), 256, 0, stream>>>(
+      reinterpret_cast<const float4*>(g), reinterpret_cast<const float4*>(z), nullptr, reinterpret_cast<float4*>(dz),
+      (uint32_t)(n / 4), (uint32_t)(C / 4), (uint32_t)T, (uint32_t)C, (uint32_t)sid_base, key, p, act, act2, lens);
+  ASRX_LAUNCHED("asrx_act_dropout_lens_bwd");
 }
 
 int asrx_dwconv_fwd(const float* x, const float* w, const float* b, float* y, int64_t B, int64_t T, int64_t C,
@@ -3144,6 +3336,24 @@ int asrx_dwconv_fwd(const float* x, const float* w, const float* b, float* y, in
   if (!dwconv_dispatch(x, w, b, y, nullptr, nullptr, nullptr, nullptr, B, T, C, K, stream))
     LAUNCH_EW(dwconv_fwd_kernel, B * T * C, x, w, b, y, B, T, (int)C, (int)K);
   ASRX_LAUNCHED("asrx_dwconv_fwd");
+}
+
+// asrx_dwconv_fwd with per-sample lengths: the tiled float4 kernels only (K = 3, 5, 7, 15)
+int asrx_dwconv_lens_fwd(const float* x, const float* w, const float* b, float* y, const int32_t* lens, int64_t B,
+                         int64_t T, int64_t C, int64_t K, hipStream_t stream) {
+  ASRX_REQUIRE(K % 2 == 1 && K <= 16, "dwconv: K must be odd and <= 15");
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE((K == 3 || K == 5 || K == 7 || K == 15) && lens_vec_ok({x, y, b}, B, T, C),
+               "asrx_dwconv_lens_fwd: K of 3, 5, 7 or 15 with C %% 4 == 0, 16-byte aligned tensors and fewer than "
+               "2^31 elements");
+  ASRX_REQUIRE_LENS("asrx_dwconv_lens_fwd");
+  switch (K) {
+    case 3: dwconv_tiled_lens_fwd<3>(x, w, b, y, lens, B, T, C, stream); break;
+    case 5: dwconv_tiled_lens_fwd<5>(x, w, b, y, lens, B, T, C, stream); break;
+    case 7: dwconv_tiled_lens_fwd<7>(x, w, b, y, lens, B, T, C, stream); break;
+    default: dwconv_tiled_lens_fwd<15>(x, w, b, y, lens, B, T, C, stream); break;
+  }
+  ASRX_LAUNCHED("asrx_dwconv_lens_fwd");
 }
 
 int asrx_dwconv_bwd(const float* g, const float* x, const float* w, float* dx, float* dw, float* db, int64_t B,
@@ -3169,6 +3379,20 @@ int asrx_dwconv_pre_bwd(const float* g, const float* x, const float* z, const fl
   ASRX_LAUNCHED("asrx_dwconv_pre_bwd");
 }
 
+// asrx_dwconv_pre_bwd with per-sample lengths
+int asrx_dwconv_pre_lens_bwd(const float* g, const float* x, const float* z, const float* w, float* dz, float* dw,
+                             float* db, const int32_t* lens, int64_t B, int64_t T, int64_t C, int64_t K, int pre,
+                             hipStream_t stream) {
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE(dwconv_pre_ok(g, x, z, dz, B, T, C, K, pre),
+               "asrx_dwconv_pre_bwd: GLU -> k15 or GELU -> k3 with C %% 4 == 0, 16-byte aligned tensors and "
+               "fewer than 2^31 elements");
+  ASRX_REQUIRE_LENS("asrx_dwconv_pre_lens_bwd");
+  if (pre == DW_PRE_GLU) dwconv_pre_bwd_launch<15, DW_PRE_GLU, true>(g, x, z, w, dz, dw, db, B, T, C, stream, lens);
+  else dwconv_pre_bwd_launch<3, DW_PRE_GELU, true>(g, x, z, w, dz, dw, db, B, T, C, stream, lens);
+  ASRX_LAUNCHED("asrx_dwconv_pre_lens_bwd");
+}
+
 int asrx_bn_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd, int64_t B,
                 int64_t T, int64_t C, float eps, int use_batch_stats, hipStream_t stream) {
   if (B * T == 0) return 0;
@@ -3176,7 +3400,7 @@ int asrx_bn_fwd(const float* x, const float* w, const float* b, float* y, float*
     if (C % 4 == 0 && ((uintptr_t)x & 15) == 0) {
       const int C4 = (int)(C / 4);
       bn_stats4_kernel<<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>((const float4*)x, mean, rstd, (int)T,
-                                                                             C4, eps);
+                                                                             C4, eps, nullptr);
     } else {
       dim3 grid((unsigned)((C + 63) / 64), (unsigned)B);
       bn_stats_kernel<<<grid, 256, 0, stream>>>(x, mean, rstd, T, (int)C, eps);
@@ -3193,7 +3417,7 @@ int asrx_bn_bwd(const float* g, const float* x, const float* mean, const float* 
       ((uintptr_t)rstd & 15) == 0) {
     const int C4 = (int)(C / 4);
     bn_bwd_stats4_kernel<false><<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>(
-        (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, nullptr);
+        (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, nullptr, nullptr);
   } else {
     dim3 grid((unsigned)((C + 63) / 64), (unsigned)B);
     bn_bwd_stats_kernel<<<grid, 256, 0, stream>>>(g, x, mean, rstd, w, sg_ws, sgx_ws, dw, db, T, (int)C);
@@ -3216,11 +3440,30 @@ int asrx_bn_silu_fwd(const float* x, const float* w, const float* b, float* y, f
   const int C4 = (int)(C / 4);
   if (use_batch_stats)
     bn_stats4_kernel<<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>((const float4*)x, mean, rstd, (int)T, C4,
-                                                                           eps);
+                                                                           eps, nullptr);
   const int64_t n4 = B * T * C4;
   LAUNCH_EW(bn_silu_apply4_kernel, n4, (const float4*)x, mean, rstd, w, b, (float4*)y, (uint32_t)n4, (uint32_t)C4,
-            (uint32_t)T, use_batch_stats);
+            (uint32_t)T, use_batch_stats, nullptr);
   ASRX_LAUNCHED("asrx_bn_silu_fwd");
+}
+
+// asrx_bn_silu_fwd with per-sample lengths: the statistics of each sample's live rows (train mode only: the
+// eval-mode apply with running statistics is row-local and needs no lengths)
+int asrx_bn_silu_lens_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd,
+                          const int32_t* lens, int64_t B, int64_t T, int64_t C, float eps, int use_batch_stats,
+                          hipStream_t stream) {
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE(bn_silu_vec_ok({x, w, b, y, mean, rstd}, B, T, C),
+               "asrx_bn_silu_fwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
+  ASRX_REQUIRE(use_batch_stats != 0, "asrx_bn_silu_lens_fwd: train-mode statistics only");
+  ASRX_REQUIRE_LENS("asrx_bn_silu_lens_fwd");
+  const int C4 = (int)(C / 4);
+  bn_stats4_kernel<true><<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>((const float4*)x, mean, rstd, (int)T,
+                                                                               C4, eps, lens);
+  const int64_t n4 = B * T * C4;
+  LAUNCH_EW(bn_silu_apply4_kernel<true>, n4, (const float4*)x, mean, rstd, w, b, (float4*)y, (uint32_t)n4,
+            (uint32_t)C4, (uint32_t)T, 1, lens);
+  ASRX_LAUNCHED("asrx_bn_silu_lens_fwd");
 }
 
 int asrx_bn_silu_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
@@ -3231,11 +3474,28 @@ int asrx_bn_silu_bwd(const float* g, const float* x, const float* mean, const fl
                "asrx_bn_silu_bwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
   const int C4 = (int)(C / 4);
   bn_bwd_stats4_kernel<true><<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>(
-      (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, b);
+      (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, b, nullptr);
   const int64_t n4 = B * T * C4;
   LAUNCH_EW(bn_silu_bwd_apply4_kernel, n4, (const float4*)g, (const float4*)x, mean, rstd, w, b, sg_ws, sgx_ws,
-            (float4*)dx, (uint32_t)n4, (uint32_t)C4, (uint32_t)T);
+            (float4*)dx, (uint32_t)n4, (uint32_t)C4, (uint32_t)T, nullptr);
   ASRX_LAUNCHED("asrx_bn_silu_bwd");
+}
+
+// asrx_bn_silu_bwd with per-sample lengths
+int asrx_bn_silu_lens_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
+                          const float* b, float* sg_ws, float* sgx_ws, float* dx, float* dw, float* db,
+                          const int32_t* lens, int64_t B, int64_t T, int64_t C, hipStream_t stream) {
+  if (B * T == 0) return 0;
+  ASRX_REQUIRE(bn_silu_vec_ok({g, x, mean, rstd, w, b, sg_ws, sgx_ws, dx}, B, T, C),
+               "asrx_bn_silu_bwd: needs C %% 4 == 0, 16-byte aligned tensors and B*T*C < 2^31");
+  ASRX_REQUIRE_LENS("asrx_bn_silu_lens_bwd");
+  const int C4 = (int)(C / 4);
+  bn_bwd_stats4_kernel<true, true><<<(unsigned)(B * ((C4 + 31) / 32)), 1024, 0, stream>>>(
+      (const float4*)g, (const float4*)x, mean, rstd, w, sg_ws, sgx_ws, dw, db, (int)T, C4, b, lens);
+  const int64_t n4 = B * T * C4;
+  LAUNCH_EW(bn_silu_bwd_apply4_kernel<true>, n4, (const float4*)g, (const float4*)x, mean, rstd, w, b, sg_ws, sgx_ws,
+            (float4*)dx, (uint32_t)n4, (uint32_t)C4, (uint32_t)T, lens);
+  ASRX_LAUNCHED("asrx_bn_silu_lens_bwd");
 }
 
 int asrx_stem1_fwd(const float* x, const float* W, const float* bias, float* y, int64_t B, int64_t T, int64_t D,

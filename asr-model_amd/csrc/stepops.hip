@@ -307,6 +307,28 @@ __global__ void bn_running_kernel(const float* __restrict__ mean, const float* _
   if (c == 0 && nbt) nbt[0] += 1;
 }
 
+// The same update from statistics over per-sample lengths (asrx_bn_silu_lens_fwd): sample b's variance is unbiased
+// by T_b / (T_b - 1), T_b = clamp(lens[b], 0, T); a sample without rows adds mean 0 and variance 0.
+__global__ void bn_running_lens_kernel(const float* __restrict__ mean, const float* __restrict__ rstd,
+                                       float* __restrict__ rm, float* __restrict__ rv, int64_t* __restrict__ nbt,
+                                       const int32_t* __restrict__ lens, int B, int C, int T, float eps, float mom) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < C) {
+    float sm = 0.f, sv = 0.f;
+    for (int b = 0; b < B; ++b) {
+      const int Tb = min(max(lens[b], 0), T);
+      if (Tb == 0) continue;
+      const float unbias = (float)Tb / (float)max(Tb - 1, 1);
+      const float r = rstd[b * C + c];
+      sm += mean[b * C + c];
+      sv += (1.f / (r * r) - eps) * unbias;
+    }
+    rm[c] = (1.f - mom) * rm[c] + mom * (sm / B);
+    rv[c] = (1.f - mom) * rv[c] + mom * (sv / B);
+  }
+  if (c == 0 && nbt) nbt[0] += 1;
+}
+
 // eval-mode BatchNorm's rstd = rsqrt(running_var + eps)
 __global__ void rsqrt_eps_kernel(const float* __restrict__ v, float* __restrict__ out, int n, float eps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -511,6 +533,17 @@ int asrx_bn_running(const float* mean, const float* rstd, float* rm, float* rv, 
   bn_running_kernel<<<(unsigned)((C + 255) / 256), 256, 0, stream>>>(mean, rstd, rm, rv, nbt, (int)B, (int)C, eps,
                                                                      unbias, momentum);
   ASRX_LAUNCHED("asrx_bn_running");
+}
+
+int asrx_bn_running_lens(const float* mean, const float* rstd, float* rm, float* rv, int64_t* nbt,
+                         const int32_t* lens, int64_t B, int64_t C, int64_t T, float eps, float momentum,
+                         hipStream_t stream) {
+  if (C == 0) return 0;
+  ASRX_REQUIRE(lens != nullptr, "asrx_bn_running_lens: per-sample lengths: null table");
+  ASRX_REQUIRE(((uintptr_t)lens & 3) == 0, "asrx_bn_running_lens: per-sample lengths: table must be 4-byte aligned");
+  bn_running_lens_kernel<<<(unsigned)((C + 255) / 256), 256, 0, stream>>>(mean, rstd, rm, rv, nbt, lens, (int)B,
+                                                                          (int)C, (int)T, eps, momentum);
+  ASRX_LAUNCHED("asrx_bn_running_lens");
 }
 
 int asrx_rsqrt_eps(const float* v, float* out, int64_t n, float eps, hipStream_t stream) {

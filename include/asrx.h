@@ -620,6 +620,44 @@ int asrx_bn_silu_fwd(const float* x, const float* w, const float* b, float* y, f
 int asrx_bn_silu_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
                      const float* b, float* sg_ws, float* sgx_ws, float* dx, float* dw, float* db, int64_t B,
                      int64_t T, int64_t C, asrx_stream_t stream);
+/* ---- the encoder with per-sample lengths: a zero-padded batch computes every sample as it would alone ----
+ * `lens` is a device table of B int32, the live row count T_b of each sample, clamped to [0, T]; T stays the
+ * launch extent (grid, addressing).  Each entry point is its uniform twin (named per entry) with `lens` ahead
+ * of the sizes: sample b's rows [0, T_b) come out as the twin gives them for x[b:b+1, :T_b], bit for bit; output
+ * rows at or past T_b are stored as zeros; input rows there count as zeros and are not loaded, so nothing live
+ * depends on what they hold (NaN included).  Parameter gradients are accumulated from live rows only.  Only the
+ * float4 kernels have this form: C % 4 == 0, 16-byte aligned tensors and fewer than 2^31 elements are required
+ * (the twin's non-float4 fall-back is refused), in the twin's words where it has them; then `lens` must be
+ * non-null and 4-byte aligned.  Early returns stand where the twin has them; every check answers before anything
+ * is launched. */
+/* asrx_act_fwd / asrx_act_bwd on (B, T, C): y = live ? act(x) : 0, dx = live ? g act'(x) : 0. */
+int asrx_act_lens_fwd(const float* x, float* y, const int32_t* lens, int64_t B, int64_t T, int64_t C, int act,
+                      asrx_stream_t stream);
+int asrx_act_lens_bwd(const float* g, const float* x, float* dx, const int32_t* lens, int64_t B, int64_t T,
+                      int64_t C, int act, asrx_stream_t stream);
+/* asrx_act_dropout_fwd / asrx_act_dropout_bwd: the mask index does not depend on T; a dead row is zeros,
+ * the residual included. */
+int asrx_act_dropout_lens_fwd(const float* z, const float* res, float* y, const int32_t* lens, int64_t B, int64_t T,
+                              int64_t C, int64_t sid_base, uint32_t key, float p, int act, int act2,
+                              asrx_stream_t stream);
+int asrx_act_dropout_lens_bwd(const float* g, const float* z, float* dz, const int32_t* lens, int64_t B, int64_t T,
+                              int64_t C, int64_t sid_base, uint32_t key, float p, int act, int act2,
+                              asrx_stream_t stream);
+/* asrx_dwconv_fwd (K of 3, 5, 7 or 15: the tiled kernels) and asrx_dwconv_pre_bwd: the taps stop at T_b as they
+ * stop at T; z is not read on dead rows. */
+int asrx_dwconv_lens_fwd(const float* x, const float* w, const float* b, float* y, const int32_t* lens, int64_t B,
+                         int64_t T, int64_t C, int64_t K, asrx_stream_t stream);
+int asrx_dwconv_pre_lens_bwd(const float* g, const float* x, const float* z, const float* w, float* dz, float* dw,
+                             float* db, const int32_t* lens, int64_t B, int64_t T, int64_t C, int64_t K, int pre,
+                             asrx_stream_t stream);
+/* asrx_bn_silu_fwd with train-mode statistics (use_batch_stats must be non-zero) over each sample's rows
+ * [0, T_b), T_b = 0 giving mean 0 and rstd 0, and asrx_bn_silu_bwd with the sums and the divisor of T_b. */
+int asrx_bn_silu_lens_fwd(const float* x, const float* w, const float* b, float* y, float* mean, float* rstd,
+                          const int32_t* lens, int64_t B, int64_t T, int64_t C, float eps, int use_batch_stats,
+                          asrx_stream_t stream);
+int asrx_bn_silu_lens_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
+                          const float* b, float* sg_ws, float* sgx_ws, float* dx, float* dw, float* db,
+                          const int32_t* lens, int64_t B, int64_t T, int64_t C, asrx_stream_t stream);
 int asrx_stem1_fwd(const float* x, const float* W, const float* bias, float* y, int64_t B, int64_t T, int64_t D,
                    asrx_stream_t stream);
 int asrx_stem1_bwd(const float* g, const float* x, float* dW, float* db, int64_t B, int64_t T, int64_t D,
@@ -771,6 +809,11 @@ int asrx_wgrad_split(const float* A, int64_t lda, const void* B, int b_bf16, int
  * nbt (num_batches_tracked, int64) may be NULL.  asrx_rsqrt_eps: eval-mode rstd. */
 int asrx_bn_running(const float* mean, const float* rstd, float* rm, float* rv, int64_t* nbt, int64_t B, int64_t C,
                     int64_t T, float eps, float momentum, asrx_stream_t stream);
+/* asrx_bn_running from the statistics of asrx_bn_silu_lens_fwd: sample b's variance is unbiased by
+ * T_b / (T_b - 1), T_b = lens[b] clamped to [0, T] (B int32 on the device, non-null and 4-byte aligned). */
+int asrx_bn_running_lens(const float* mean, const float* rstd, float* rm, float* rv, int64_t* nbt,
+                         const int32_t* lens, int64_t B, int64_t C, int64_t T, float eps, float momentum,
+                         asrx_stream_t stream);
 int asrx_rsqrt_eps(const float* v, float* out, int64_t n, float eps, asrx_stream_t stream);
 /* k3 Conv1d weight (Co, Ci, 3), weight-normed when g != NULL (W = g v/|v|, model.py:140), into the
  * implicit-im2col GEMM layouts: Wt (Co, 3Ci) k-major and Wf (Ci, 3Co) flipped, fp32 and/or bf16 (each
