@@ -334,15 +334,20 @@ def gemm_wn_rows(A, Wb, C, *, M, N, K, lda, ldc, mtiles, bias=None, alpha=1.0, b
     return gemm_wn(A, Wb, C, M=M, N=N, K=K, lda=lda, ldc=ldc, bias=bias, alpha=alpha, beta=beta, mtiles=mtiles)
 
 
-def row_tiles(next_i, layer, L, M, device=None):
+def row_tiles(next_i, layer, L, M, device=None, lens=None):
     """(list, count) of the 128-row tiles of an M-row activation holding rows of samples at MSheath
     layer `layer` (next_i[b] == layer, L rows per sample), built on the device.  next_i: a tensor, or a device
-    address with `device` given."""
+    address with `device` given.  lens (the (B,) int32 device table of ops.seq_lens): only tiles holding a live
+    row, l < lens[b], of such a sample."""
     n = int(lib.load().asrx_row_tiles_max(M))
     dev = device if device is not None else next_i.device
     tl = torch.empty(n, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int32, device=dev)
-    lib.call("asrx_row_tiles", lib.ptr(next_i), layer, L, M, lib.ptr(tl), lib.ptr(cnt), lib.stream())
+    if lens is not None:
+        lib.call("asrx_row_lens_tiles", lib.ptr(next_i), layer, lib.ptr(lens), L, M, lib.ptr(tl), lib.ptr(cnt),
+                 lib.stream())
+    else:
+        lib.call("asrx_row_tiles", lib.ptr(next_i), layer, L, M, lib.ptr(tl), lib.ptr(cnt), lib.stream())
     return tl, cnt
 
 

@@ -160,6 +160,25 @@ SIGNATURES = {
     "asrx_dwconv_pre_lens_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
     "asrx_bn_silu_lens_fwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _i32, _p]),
     "asrx_bn_silu_lens_bwd": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "asrx_seg_colsum_lens_det": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "asrx_msheath_row_lens_fwd2": (_i32, [_p] * 6 + [_i64] + [_p] * 7 + [_i32] + [_p] * 8 + [_i64] * 4
+                                         + [_f32, _f32, _p, _i64, _i64, _p]),
+    "asrx_msheath_row_lens_fwd3": (_i32, [_p] * 6 + [_i64] + [_p] * 17 + [_i64] * 4 + [_f32, _f32, _p, _i64, _i64, _p]),
+    "asrx_msheath_row_lens_bwd2": (_i32, [_i32] + [_p] * 15 + [_i64] + [_p] * 19 + [_i64] * 4
+                                         + [_f32, _p, _i64, _i64, _p]),
+    "asrx_axpy_lens_row": (_i32, [_p] * 5 + [_i64] * 3 + [_p]),
+    "asrx_axpy_lens_row_bwd2": (_i32, [_p] * 7 + [_i64] * 3 + [_p]),
+    "asrx_axpy_row2_lens_colsum": (_i32, [_p] * 7 + [_i64] * 3 + [_p, _i64, _p]),
+    "asrx_msheath_ctrl_lens_fwd3": (_i32, [_p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]
+                                          + [_i64, _i64, _p, _i64, _i64, _i64] + [_p] * 8),
+    "asrx_jump_lens_select4": (_i32, [_p] * 9 + [_i64] * 3 + [_p]),
+    "asrx_jump_lens_axpy_inplace": (_i32, [_p] * 11 + [_i64] * 3 + [_p]),
+    "asrx_jump_lens_select4_bwd_part2": (_i32, [_p] * 12 + [_i64] * 3 + [_p]),
+    "asrx_msheath_ctrl_lens_bwd4": (_i32, [_p, _p, _i64, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _p, _i32]
+                                          + [_p] * 8),
+    "asrx_axpy_row2_lens_bwd_acc2": (_i32, [_p] * 12 + [_i64] * 3 + [_p]),
+    "asrx_msheath_lens_dx_final": (_i32, [_p] * 5 + [_i64] * 3 + [_p]),
+    "asrx_row_lens_tiles": (_i32, [_p, _i64, _p, _i64, _i64, _p, _p, _p]),
     "asrx_stem1_fwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_stem1_bwd": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "asrx_embed_fwd": (_i32, [_p, _p, _p, _i64, _i64, _p]),

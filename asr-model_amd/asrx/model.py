@@ -420,14 +420,21 @@ class MSheath(nn.Module):
     # per-op composition below (same kernels and results; kept as the reference implementation of it)
     fused = True
 
-    def run(self, x, noise: NoiseCtx, site: str, sid_base: int):
+    def run(self, x, noise: NoiseCtx, site: str, sid_base: int, lens=None):
         """Batched MSheath.forward with batch-1 semantics per sample: every sample follows its own
-        layer/jump trajectory, evaluated as masked compute on device (no host syncs)."""
+        layer/jump trajectory, evaluated as masked compute on device (no host syncs).
+        lens (ops.seq_lens): per-sample row counts of a zero-padded batch; sample b's rows [0, T_b) then come out,
+        and its gradient, bit for bit as run(x[b:b+1, :T_b], noise, site, sid_base + b) gives them, rows at or past
+        T_b are zeros, and x's pad rows must be finite (their values reach no result).  Only the fused path takes
+        lengths: the composed path raises ValueError instead of ignoring them."""
         from . import msheath as _ms
 
         if self.fused and ops.DIRECT and _ms.supported(self, x.shape[-1]):
             gpol = ops.policy_noise(x.shape[0], self.layer, sid_base, noise.key(site), x.device)
-            return _ms.msheath(self, x, gpol, tag=(noise.key(site), sid_base))
+            return _ms.msheath(self, x, gpol, tag=(noise.key(site), sid_base), lens=lens)
+        if lens is not None and not lens.check(x.shape[0], x.shape[1], x.device):
+            raise ValueError("MSheath.run: lens needs the fused path (MSheath.fused, ops.DIRECT and a width in "
+                             f"msheath.ROW_DIMS); got fused={self.fused}, D={x.shape[-1]}")
         return self.run_composed(x, noise, site, sid_base)
 
     def run_composed(self, x, noise: NoiseCtx, site: str, sid_base: int):

@@ -85,9 +85,36 @@ def _params(mod):
 ACT_SOFTMAX = 16  # csrc/common.h
 
 
-def forward(mod, x0, gpol, save, tag=None):
+def _live_lens(lens, x):
+    """lens of a MSheath call on x (B, L, D) -> None when absent or every sample is full length (today's calls and
+    kernels, untouched), else lens after the checks of the LENS path: a call it cannot take is an error, never a
+    fall-back to kernels that would ignore the lengths."""
+    if lens is None:
+        return None
+    if not isinstance(lens, ops.SeqLens):
+        raise TypeError(f"msheath: lens must come from ops.seq_lens, got {type(lens).__name__}")
+    if x.dim() != 3:
+        raise ValueError(f"msheath: lens needs a (B, L, D) tensor, got {tuple(x.shape)}")
+    if lens.check(x.shape[0], x.shape[1], x.device):  # wrong count, a length above L: ValueError
+        return None
+    if not DETERMINISTIC:
+        raise ValueError("msheath: lens needs the ordered jump sums (msheath.DETERMINISTIC is False)")
+    if decisions.active():
+        raise ValueError("msheath: lens with an active asrx.decisions recorder is not supported")
+    if x.shape[-1] not in ROW_DIMS:
+        raise ValueError(f"msheath: lens needs a width in {ROW_DIMS}, got {x.shape[-1]}")
+    return lens
+
+
+def forward(mod, x0, gpol, save, tag=None, lens=None, vetted=False):
     """MSheath forward on (B, L, D) x0 with policy noise gpol (B, layers, 3).  Returns (out, saved).
-    tag: (noise site key, sid_base) of the call, for asrx.decisions."""
+    tag: (noise site key, sid_base) of the call, for asrx.decisions.
+    lens (ops.SeqLens; None or all-full: the calls below unchanged): sample b's rows [0, T_b) come out as for
+    x0[b:b+1, :T_b] alone, the pooled, mem and ion means taken over them; rows at or past T_b are not read (those of
+    x0 must be finite: the GEMMs pass over them) and are zeros in everything stored."""
+    if not vetted:  # (msheath() and MSheathFn hand over what _live_lens returned)
+        lens = _live_lens(lens, x0)
+    lt = lens.table if lens is not None else None
     B, L, D = x0.shape
     rows = B * L
     dev = x0.device
@@ -97,7 +124,10 @@ def forward(mod, x0, gpol, save, tag=None):
     nchunk = int(lib.load().asrx_mem_chunks(L))
     part = _E(len(mod.layers) + 1, B, nchunk, D, device=dev)  # row-chunk column sums (deterministic means)
     pooled = _E(B, D, device=dev)
-    lib.call("asrx_seg_colsum_det", _P(x0), _P(part[-1]), _P(pooled), B, L, D, 1.0 / L, st)
+    if lt is not None:
+        lib.call("asrx_seg_colsum_lens_det", _P(x0), _P(part[-1]), _P(pooled), _P(lt), B, L, D, st)
+    else:
+        lib.call("asrx_seg_colsum_det", _P(x0), _P(part[-1]), _P(pooled), B, L, D, 1.0 / L, st)
     net = mod.pnet.net
     zp = _E(B, net[0].weight.shape[0], device=dev) if save else None
     hp = G.linear_fwd(pooled, net[0].weight, net[0].bias, act="silu", preact=zp)
@@ -122,6 +152,7 @@ def forward(mod, x0, gpol, save, tag=None):
     if save:
         sv["ws"] = (wsr, wsb, wsd, wsc)
         sv["bwd_fused"] = BWD_FUSED  # the backward follows what this forward stored
+        sv["lens"] = lens
     inv_sqrt_d = 1.0 / math.sqrt(D)
     layers = []
     for i, lay in enumerate(mod.layers):
@@ -141,7 +172,8 @@ def forward(mod, x0, gpol, save, tag=None):
         Wc, bc, mkn, wb = G.derived(("vgate", bool(wide)), build, (vg.mkey, vg.mlp[0].weight, vg.mlp[0].bias))
         # rows of samples not at this layer (next_i[b] != i; the reference never runs them) are skipped:
         # by whole 128-row tiles in the GEMMs, by row in the row kernels
-        mt = G.row_tiles(next_i, i, L, rows, dev) if (wide and next_i is not None) else None
+        # (with lens: by 128-row tiles holding no live row too; layer 0 keeps the plain GEMM, as the sample alone)
+        mt = G.row_tiles(next_i, i, L, rows, dev, lens=lt) if (wide and next_i is not None) else None
         SH = G.linear_fwd(x, Wc, bc, wbf=wb, mtiles=mt)
         # px = LayerNorm(x), |x|, g = sigmoid(gate(px)), ion = v_gate(x)   (346-351, 452-460)
         ln, gt = lay["ln"], lay["gate"][0]
@@ -155,7 +187,23 @@ def forward(mod, x0, gpol, save, tag=None):
         # x_new = x + g * ion * out; mem = mean_l x_new   (461-463).  Without a backward x_new is not
         # materialised: the column sums are taken and the jump step below recomputes it
         x_new = _E(B, L, D, device=dev) if save else None
-        if ad is None and ROW_COLSUM:  # out = px: the row pass forms x_new and its column sums itself
+        if lt is not None:  # the same launches from the LENS entry points
+            if ad is None and ROW_COLSUM:
+                lib.call("asrx_msheath_row_lens_fwd3", _P(x), _P(ln.weight), _P(ln.bias), _P(gt.weight), _P(gt.bias),
+                         _P(SH), N, _P(vg.mval), _P(vg.mlp[2].weight), _P(vg.mlp[2].bias), _P(vg.concat.weight),
+                         _P(vg.concat.bias), _P(vg.tx), _P(px), _P(mean), _P(rstd), _P(nx), _P(gv), _P(ion), _P(kv),
+                         _P(m2), _P(x_new), _P(part[i]), _P(lt), rows, D, M, Dh, float(ln.eps), inv_sqrt_d, _P(next_i),
+                         i, L, st)
+                out = px
+            else:
+                lib.call("asrx_msheath_row_lens_fwd2", _P(x), _P(ln.weight), _P(ln.bias), _P(gt.weight), _P(gt.bias),
+                         _P(SH), N, _P(vg.mval), _P(vg.mlp[2].weight), _P(vg.mlp[2].bias), _P(vg.concat.weight),
+                         _P(vg.concat.bias), _P(vg.tx), _P(px), pxb, _P(mean), _P(rstd), _P(nx), _P(gv), _P(ion),
+                         _P(kv), _P(m2), _P(lt), rows, D, M, Dh, float(ln.eps), inv_sqrt_d, _P(next_i), i, L, st)
+                out = G.linear_fwd(px, ad.weight, ad.bias, mtiles=mt) if ad is not None else px
+                lib.call("asrx_axpy_row2_lens_colsum", _P(x), _P(gv), _P(ion), _P(out), _P(x_new), _P(part[i]), _P(lt),
+                         B, L, D, _P(next_i), i, st)
+        elif ad is None and ROW_COLSUM:  # out = px: the row pass forms x_new and its column sums itself
             lib.call("asrx_msheath_row_fwd3", _P(x), _P(ln.weight), _P(ln.bias), _P(gt.weight), _P(gt.bias), _P(SH),
                      N, _P(vg.mval), _P(vg.mlp[2].weight), _P(vg.mlp[2].bias), _P(vg.concat.weight),
                      _P(vg.concat.bias), _P(vg.tx), _P(px), _P(mean), _P(rstd), _P(nx), _P(gv), _P(ion), _P(kv), _P(m2),
@@ -174,19 +222,32 @@ def forward(mod, x0, gpol, save, tag=None):
         gam, mwo, mem = (a_d + 4 * B * D * (3 * i + j) for j in range(3))
         rec = a_c + B * rec_bytes * i
         gp = gpol[:, i]
-        lib.call("asrx_msheath_ctrl_fwd3", _P(policy), _P(gp), gp.stride(0), _P(ion), _P(mg.weight), _P(mg.bias),
-                 _P(mem_v), _P(mem_w), ld_mw, _P(part[i]), _P(mem), _P(mod.jump_s), _P(next_i), i, nl, B, L, D,
-                 _P(alpha), _P(beta), _P(gam), _P(mwo), _P(active), _P(next_out), _P(rec), st)
+        if lt is not None:
+            lib.call("asrx_msheath_ctrl_lens_fwd3", _P(policy), _P(gp), gp.stride(0), _P(ion), _P(mg.weight),
+                     _P(mg.bias), _P(mem_v), _P(mem_w), ld_mw, _P(part[i]), _P(mem), _P(mod.jump_s), _P(next_i), i, nl,
+                     _P(lt), B, L, D, _P(alpha), _P(beta), _P(gam), _P(mwo), _P(active), _P(next_out), _P(rec), st)
+        else:
+            lib.call("asrx_msheath_ctrl_fwd3", _P(policy), _P(gp), gp.stride(0), _P(ion), _P(mg.weight), _P(mg.bias),
+                     _P(mem_v), _P(mem_w), ld_mw, _P(part[i]), _P(mem), _P(mod.jump_s), _P(next_i), i, nl, B, L, D,
+                     _P(alpha), _P(beta), _P(gam), _P(mwo), _P(active), _P(next_out), _P(rec), st)
         if tag is not None and decisions.active():
             decisions.msheath_layer(tag[0], tag[1], i, wsr[i, 4].view(B, L), wsc[i].view(torch.float32).view(B, -1))
         if save:
             x_out = _E(B, L, D, device=dev)
-            lib.call("asrx_jump_select4", _P(x_new), _P(x0), _P(x), _P(active), _P(alpha), _P(beta), _P(gam),
-                     _P(x_out), B, L, D, st)
+            if lt is not None:
+                lib.call("asrx_jump_lens_select4", _P(x_new), _P(x0), _P(x), _P(active), _P(alpha), _P(beta), _P(gam),
+                         _P(x_out), _P(lt), B, L, D, st)
+            else:
+                lib.call("asrx_jump_select4", _P(x_new), _P(x0), _P(x), _P(active), _P(alpha), _P(beta), _P(gam),
+                         _P(x_out), B, L, D, st)
         else:  # one pass, in place from layer 1 on (samples not at the layer keep their rows untouched)
             x_out = _E(B, L, D, device=dev) if i == 0 else x
-            lib.call("asrx_jump_axpy_inplace", _P(x), _P(x_out), _P(gv), _P(ion), _P(out), _P(x0), _P(active),
-                     _P(alpha), _P(beta), _P(gam), B, L, D, st)
+            if lt is not None:  # (layer 0, out of place, stores the zero pad rows; in place they stay)
+                lib.call("asrx_jump_lens_axpy_inplace", _P(x), _P(x_out), _P(gv), _P(ion), _P(out), _P(x0), _P(active),
+                         _P(alpha), _P(beta), _P(gam), _P(lt), B, L, D, st)
+            else:
+                lib.call("asrx_jump_axpy_inplace", _P(x), _P(x_out), _P(gv), _P(ion), _P(out), _P(x0), _P(active),
+                         _P(alpha), _P(beta), _P(gam), B, L, D, st)
         if save:
             layers.append(dict(x=x, Wc=Wc, mkn=mkn, SH=SH, nx=nx, kv=kv, m2=m2, px=px, mean=mean, rstd=rstd,
                                out=out, g=gv, ion=ion, x_new=x_new, mem=mem, mem_v=mem_v, mem_w=mem_w, ld_mw=ld_mw,
@@ -208,7 +269,10 @@ def forward(mod, x0, gpol, save, tag=None):
                       out_bf16=prec.bf16_storage())
     hh = G.linear_fwd(a1, mod.mlp[2].weight, mod.mlp[2].bias)
     y = _E(B, L, D, device=dev)
-    lib.call("asrx_axpy_row", _P(x), _P(gate), _P(hh), _P(y), rows, D, st)
+    if lt is not None:  # pad rows of y are zeros (the tail's LayerNorm and GEMMs ran over zero rows)
+        lib.call("asrx_axpy_lens_row", _P(x), _P(gate), _P(hh), _P(y), _P(lt), B, L, D, st)
+    else:
+        lib.call("asrx_axpy_row", _P(x), _P(gate), _P(hh), _P(y), rows, D, st)
     if save:
         sv.update(x0=x0, pooled=pooled, zp=zp, hp=hp, policy=policy, layers=layers, x=x, gate=gate, hln=hln,
                   mean2=mean2, rstd2=rstd2, z1=z1, a1=a1, hh=hh)
@@ -217,9 +281,9 @@ def forward(mod, x0, gpol, save, tag=None):
 
 class MSheathFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x0, gpol, mod, tag, *params):
+    def forward(ctx, x0, gpol, mod, tag, lens, *params):
         x0 = x0 if x0.is_contiguous() else x0.contiguous()
-        y, sv = forward(mod, x0, gpol, save=True, tag=tag)
+        y, sv = forward(mod, x0, gpol, save=True, tag=tag, lens=lens, vetted=True)
         ctx.mod, ctx.sv = mod, sv
         return y
 
@@ -234,6 +298,10 @@ class MSheathFn(torch.autograd.Function):
         dev = x0.device
         st = _S()
         touched = []
+        # per-sample lengths: the LENS entry points below.  g_mem / T_b and dpooled / T_b go to live rows only, every
+        # sum takes live rows only, pad rows of gy are not read, and each gradient buffer's first writer stores zeros
+        # in its pad rows (the tail's GEMMs, LayerNorm and weight gradients then see zero rows)
+        lt = sv["lens"].table if sv["lens"] is not None else None
 
         def gb(p):  # accumulation target p.grad (created zeroed on first use)
             touched.append(p)
@@ -244,7 +312,11 @@ class MSheathFn(torch.autograd.Function):
         dx = _E(B, L, D, device=dev)
         dhh = _E(B, L, D, device=dev)
         dgate = _E(rows, device=dev)
-        lib.call("asrx_axpy_row_bwd2", _P(gy), _P(sv["gate"]), _P(sv["hh"]), _P(dhh), _P(dgate), _P(dx), rows, D, st)
+        if lt is not None:
+            lib.call("asrx_axpy_lens_row_bwd2", _P(gy), _P(sv["gate"]), _P(sv["hh"]), _P(dhh), _P(dgate), _P(dx), _P(lt),
+                     B, L, D, st)
+        else:
+            lib.call("asrx_axpy_row_bwd2", _P(gy), _P(sv["gate"]), _P(sv["hh"]), _P(dhh), _P(dgate), _P(dx), rows, D, st)
         mg = mod.mlp_gate[0]
         lib.call("asrx_small_linear_bwd", _P(dgate), _P(sv["gate"]), _P(x), _P(mg.weight), _P(dx), _P(gb(mg.weight)),
                  _P(gb(mg.bias)), rows, D, 1, SIG, 1.0, st)
@@ -290,7 +362,16 @@ class MSheathFn(torch.autograd.Function):
             dxi = _E(B, L, D, device=dev)
             dxn = None if fused else _E(B, L, D, device=dev)  # fused: alpha g is formed by its consumers
             g_mem_w, g_mem = _E(B, D, device=dev), _E(B, D, device=dev)
-            if DETERMINISTIC:  # per-chunk partials summed in order by the control backward
+            if lt is not None:  # (the forward refused lengths without DETERMINISTIC)
+                part = _E(int(lib.load().asrx_jump_bwd_part_floats(B, L, D)), device=dev)
+                lib.call("asrx_jump_lens_select4_bwd_part2", _P(dx), _P(s["x_new"]), _P(x0), _P(s["active"]),
+                         _P(s["alpha"]), _P(s["beta"]), _P(has_orig), _P(dxn), _P(dorig), _P(dxi), _P(part), _P(lt),
+                         B, L, D, st)
+                lib.call("asrx_msheath_ctrl_lens_bwd4", _P(part), _P(lt), L, _P(g_mwo), _P(s["mem_v"]), _P(s["mem_w"]),
+                         s["ld_mw"], _P(s["mem"]), _P(mod.jump_s), _P(s["rec"]), i, nl, B, D, _P(g_policy),
+                         int(i != nl - 1), _P(g_mem_w), _P(g_mem), _P(gb(mod.jump_s)), _P(has_orig), _P(mg_w),
+                         _P(gb(mg_w)), _P(gb(mg_b)), st)
+            elif DETERMINISTIC:  # per-chunk partials summed in order by the control backward
                 part = _E(int(lib.load().asrx_jump_bwd_part_floats(B, L, D)), device=dev)
                 lib.call("asrx_jump_select4_bwd_part2" if fused else "asrx_jump_select4_bwd_part",
                          _P(dx), _P(s["x_new"]), _P(x0), _P(s["active"]), _P(s["alpha"]), _P(s["beta"]), _P(has_orig),
@@ -312,7 +393,15 @@ class MSheathFn(torch.autograd.Function):
             ad = lay["adapter"]
             mode = 2 if fused and ad is None else 0  # asrx_msheath_row_bwd2's mode
             dout = dgv = dion = None
-            if not fused:
+            if lt is not None and (not fused or ad is not None):  # one entry point, alpha when g arrives unscaled
+                dout = _E(B, L, D, device=dev)
+                dgv, dion = _E(rows, device=dev), _E(rows, device=dev)
+                lib.call("asrx_axpy_row2_lens_bwd_acc2", _P(dx if fused else dxn), _P(s["alpha"]) if fused else None,
+                         _P(g_mem), _P(s["active"]), _P(s["g"]), _P(s["ion"]), _P(s["out"]), _P(dout), _P(dgv),
+                         _P(dion), _P(dxi), _P(lt), B, L, D, st)
+            elif lt is not None:
+                pass
+            elif not fused:
                 dout = _E(B, L, D, device=dev)
                 dgv, dion = _E(rows, device=dev), _E(rows, device=dev)
                 lib.call("asrx_axpy_row2_bwd_acc", _P(dxn), _P(g_mem), 1.0 / L, _P(s["active"]), _P(s["g"]),
@@ -337,7 +426,11 @@ class MSheathFn(torch.autograd.Function):
                         _P(gb(gt.weight)), _P(gb(gt.bias)), _P(dSH), _P(gb(vg.mval)), _P(gb(vg.mlp[2].weight)),
                         _P(gb(vg.mlp[2].bias)), _P(gb(vg.concat.weight)), _P(gb(vg.concat.bias)),
                         _P(gb(vg.mlp[0].bias)), rows, D, M, Dh, inv_sqrt_d, _P(s["next_i"]), i, L, st)
-            if mode:
+            if lt is not None:  # both modes from one entry point; 1 / T_b is formed on the device
+                lib.call("asrx_msheath_row_lens_bwd2", mode, _P(dx) if mode else None,
+                         _P(s["alpha"]) if mode else None, _P(g_mem) if mode else None,
+                         _P(s["ion"]) if mode else None, *row_args[:-9], _P(lt), *row_args[-9:])
+            elif mode:
                 # no adapter (dpx, dgv, dion are None): dxi's base g' formed from (dx, alpha, g_mem / L) in the row
                 # pass, which is dxi's first writer for samples at the layer, and the x_new backward done there on px
                 # recomputed from x, mean and rstd
@@ -374,16 +467,19 @@ class MSheathFn(torch.autograd.Function):
         dpooled = G.linear_dgrad(dhp, net[0].weight)
         G.linear_wgrad(dhp, sv["pooled"], out=gb(net[0].weight), accumulate=True)
         ops.colsum(dhp, out=gb(net[0].bias))
-        u = _E(B, D, device=dev)
-        lib.call("asrx_lincomb", _P(dpooled), None, None, 1.0 / L, 0.0, 0.0, _P(u), B * D, st)
-        lib.call("asrx_msheath_dx_final", _P(dx), _P(dorig), _P(has_orig), _P(u), B, L, D, st)
+        if lt is not None:  # u = dpooled / T_b formed in the pass, pad rows of dx stored as zeros
+            lib.call("asrx_msheath_lens_dx_final", _P(dx), _P(dorig), _P(has_orig), _P(dpooled), _P(lt), B, L, D, st)
+        else:
+            u = _E(B, D, device=dev)
+            lib.call("asrx_lincomb", _P(dpooled), None, None, 1.0 / L, 0.0, 0.0, _P(u), B * D, st)
+            lib.call("asrx_msheath_dx_final", _P(dx), _P(dorig), _P(has_orig), _P(u), B, L, D, st)
         # announce each parameter's accumulated gradient once (asrx.dist.GradSync counts events)
         seen = set()
         for p in touched:
             if id(p) not in seen:
                 seen.add(id(p))
                 ops._gret(p, p.grad, True)
-        return (dx, None, None, None) + (None,) * len(ctx.needs_input_grad[4:])
+        return (dx, None, None, None, None) + (None,) * len(ctx.needs_input_grad[5:])
 
 
 # ------------------------------------------------------------------------------------------------ no-save composite
@@ -480,15 +576,18 @@ def _forward_composite(mod, x0, gpol):
     return y
 
 
-def msheath(mod, x, gpol, tag=None):
+def msheath(mod, x, gpol, tag=None, lens=None):
     """Fused MSheath call.  Without autograd (the reference's dead blocks, eval, decoding) the forward
     runs without saving anything for a backward -- from C++ in one call where it can (_forward_composite).
-    tag: (noise site key, sid_base) for asrx.decisions."""
+    tag: (noise site key, sid_base) for asrx.decisions.
+    lens (ops.seq_lens): per-sample row counts of a zero-padded batch (forward()); None or all-full changes nothing.
+    With live lengths the no-grad forward is the Python loop (the composite call does not take lengths)."""
+    lens = _live_lens(lens, x)
     if not torch.is_grad_enabled():
         x = x if x.is_contiguous() else x.contiguous()
-        if _composite_ok(mod, x, gpol, tag):
+        if lens is None and _composite_ok(mod, x, gpol, tag):
             return _forward_composite(mod, x, gpol)
-        return forward(mod, x, gpol, save=False, tag=tag)[0]
+        return forward(mod, x, gpol, save=False, tag=tag, lens=lens, vetted=True)[0]
     # the parameter list (~60 nn.Module attribute walks) is made once per module: the module tree is fixed
     params = mod.__dict__.get("_asrx_params")
     if params is None or params[4] is not mod.mem_w or params[7] is not mod.jump_s:  # (replaced parameters)
@@ -496,7 +595,7 @@ def msheath(mod, x, gpol, tag=None):
         mod.__dict__["_asrx_params"] = params
     if not (x.requires_grad or any(p.requires_grad for p in params)):
         x = x if x.is_contiguous() else x.contiguous()
-        if _composite_ok(mod, x, gpol, tag):
+        if lens is None and _composite_ok(mod, x, gpol, tag):
             return _forward_composite(mod, x, gpol)
-        return forward(mod, x, gpol, save=False, tag=tag)[0]
-    return MSheathFn.apply(x, gpol, mod, tag, *params)
+        return forward(mod, x, gpol, save=False, tag=tag, lens=lens, vetted=True)[0]
+    return MSheathFn.apply(x, gpol, mod, tag, lens, *params)

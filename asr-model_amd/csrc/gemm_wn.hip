@@ -380,9 +380,13 @@ extern "C" int asrx_gemm_wn_rows(const float* A, int64_t lda, const unsigned sho
 
 // The BM-row tiles of an M-row activation whose rows r belong to a sample b = r / L that is at MSheath
 // layer `layer` (next_i[b] == layer): mtiles[0 .. *n_mtiles) in increasing order.  One workgroup.
+// LENS (asrx_row_lens_tiles; next_i may be null: every sample at the layer): a tile is listed only if it holds a live
+// row, l < T_b = lens[b] clamped to [0, L], of a sample at the layer -- all-pad tiles are skipped like inactive samples.
 namespace asrx {
+template <bool LENS = false>
 __global__ __launch_bounds__(1024) void row_tiles_kernel(const float* __restrict__ next_i, int layer, int64_t L,
-                                                         int64_t M, int* __restrict__ mtiles, int* __restrict__ n_out) {
+                                                         int64_t M, int* __restrict__ mtiles, int* __restrict__ n_out,
+                                                         const int32_t* __restrict__ lens = nullptr) {
   __shared__ int wsum[16];
   __shared__ int base;
   const int nm = (int)((M + wn::BM - 1) / wn::BM);
@@ -393,7 +397,15 @@ __global__ __launch_bounds__(1024) void row_tiles_kernel(const float* __restrict
     int act = 0;
     if (t < nm) {
       const int64_t r0 = (int64_t)t * wn::BM, r1 = min<int64_t>(r0 + wn::BM, M) - 1;
-      for (int64_t b = r0 / L; b <= r1 / L && !act; ++b) act = next_i[b] == (float)layer;
+      if constexpr (LENS) {
+        for (int64_t b = r0 / L; b <= r1 / L && !act; ++b) {
+          const int64_t Tb = min<int64_t>(max(lens[b], 0), L);
+          // the sample's live rows [b L, b L + T_b) meet the tile's [r0, r1]
+          act = (!next_i || next_i[b] == (float)layer) && b * L + Tb > r0 && b * L <= r1 && Tb > 0;
+        }
+      } else {
+        for (int64_t b = r0 / L; b <= r1 / L && !act; ++b) act = next_i[b] == (float)layer;
+      }
     }
     // block exclusive scan of act
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -424,8 +436,17 @@ extern "C" int64_t asrx_row_tiles_max(int64_t M) { return (M + wn::BM - 1) / wn:
 extern "C" int asrx_row_tiles(const float* next_i, int64_t layer, int64_t L, int64_t M, int* mtiles, int* n_mtiles,
                               hipStream_t stream) {
   ASRX_REQUIRE(L > 0 && M > 0, "asrx_row_tiles: empty");
-  row_tiles_kernel<<<1, 1024, 0, stream>>>(next_i, (int)layer, L, M, mtiles, n_mtiles);
+  row_tiles_kernel<false><<<1, 1024, 0, stream>>>(next_i, (int)layer, L, M, mtiles, n_mtiles);
   ASRX_LAUNCHED("asrx_row_tiles");
+}
+
+extern "C" int asrx_row_lens_tiles(const float* next_i, int64_t layer, const int32_t* lens, int64_t L, int64_t M,
+                                   int* mtiles, int* n_mtiles, hipStream_t stream) {
+  ASRX_REQUIRE(L > 0 && M > 0, "asrx_row_tiles: empty");
+  ASRX_REQUIRE(lens != nullptr, "asrx_row_lens_tiles: per-sample lengths: null table");
+  ASRX_REQUIRE(((uintptr_t)lens & 3) == 0, "asrx_row_lens_tiles: per-sample lengths: table must be 4-byte aligned");
+  row_tiles_kernel<true><<<1, 1024, 0, stream>>>(next_i, (int)layer, L, M, mtiles, n_mtiles, lens);
+  ASRX_LAUNCHED("asrx_row_lens_tiles");
 }
 
 // AbbyNormal router (essentials.py:155-161) in one pass: h_pre = A W1^T + b1 (kept in hpre when

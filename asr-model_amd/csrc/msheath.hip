@@ -20,6 +20,22 @@ struct CtrlRec {
   float act;      // sample was at this layer
 };
 
+// Per-sample lengths (the LENS instantiations below; asrx_*_lens_* entry points): sample b's live row count T_b of the
+// (B,) int32 device table, clamped to the launch extent L so that a bad table cannot address past it.  L keeps the
+// grid, the addressing and the slots of the chunk partials; T_b takes its place as the row limit and in the means'
+// divisors.  A row at or past T_b is treated exactly like a row of a sample that is not at the layer: not read, and
+// stored as zeros where this kernel is the buffer's first writer.  Sums over rows take the chunks that hold live rows
+// only -- a prefix of the slots -- in the uniform order, so sample b comes out as it would from x[b, :T_b] alone.
+__device__ __forceinline__ int seq_len(const int32_t* __restrict__ lens, int64_t b, int L) {
+  return min(max(lens[b], 0), L);
+}
+// 1 / T_b as the uniform kernels' callers pass 1.0 / L (float(1.0 / L) == 1.0f / float(L) for every L < 2^24,
+// tests/test_msheath_lens_ref.py); 0 for an empty sample, whose means are then 0
+__device__ __forceinline__ float seq_rcp(int Tb) { return Tb > 0 ? 1.0f / (float)Tb : 0.f; }
+
+constexpr int MEM_CHUNK = 64;   // rows per mem-mean chunk partial (axpy_row2_colsum_kernel, the row forward)
+constexpr int JUMP_CHUNK = 128;  // rows per jump-backward chunk partial (the launchers' lchunk)
+
 // Forward.  grid B, 256 threads.  policy (B,3), gpol (B,3) with row stride ld_gpol (the noise of
 // this layer), ion (B,L) the v_gate output, mem_v (B) sigmoid(mem_gate(mem)), mem_w / mem (B,D),
 // jump_s (3), next_i (B) float layer index.  Outputs alpha, beta (B), gam (B,D), mem_w_out (B,D),
@@ -27,7 +43,9 @@ struct CtrlRec {
 // CT: threads of the forward control kernel (one workgroup per sample): above D = 512 the mem-partial loads of 512
 // threads take half the dependent trips of 256 (8.6 vs 11.2 us at B = 8, L = 6002, D = 768); at D <= 512 the
 // 256-thread kernel is as fast or faster (7.8 vs 8.6 us at B = 32, D = 384; profiles/r06_ctrl_ab.txt)
-template <int CT>
+// LENS: mem over the first ceil(T_b / 64) chunk partials times 1 / T_b, potential over ion rows below T_b divided by
+// T_b; the ion branch is still picked by L (both branches add a thread's values in the same stride order).
+template <int CT, bool LENS = false>
 __global__ __launch_bounds__(CT) void msheath_ctrl_fwd_kernel(
     const float* __restrict__ policy, const float* __restrict__ gpol, int64_t ld_gpol, const float* __restrict__ ion,
     const float* __restrict__ mem_v, const float* __restrict__ mem_w, const float* __restrict__ mem,
@@ -35,9 +53,16 @@ __global__ __launch_bounds__(CT) void msheath_ctrl_fwd_kernel(
     float* __restrict__ alpha, float* __restrict__ beta, float* __restrict__ gam, float* __restrict__ mem_w_out,
     float* __restrict__ active, float* __restrict__ next_out, CtrlRec* __restrict__ rec, int64_t ld_mem_w,
     const float* __restrict__ mg_w, const float* __restrict__ mg_b, float* __restrict__ mem_v_out,
-    const float* __restrict__ mem_part, int nchunk, float* __restrict__ mem_out) {
+    const float* __restrict__ mem_part, int nchunk, float* __restrict__ mem_out,
+    const int32_t* __restrict__ lens = nullptr) {
   __shared__ float red[CT / 64];
   const int64_t b = blockIdx.x;
+  int64_t Lb = L;     // the sample's row limit
+  int ncb = nchunk;   // its chunk partials (nchunk stays the slot stride)
+  if constexpr (LENS) {
+    Lb = seq_len(lens, b, (int)L);
+    ncb = (int)((Lb + MEM_CHUNK - 1) / MEM_CHUNK);
+  }
   // the sample's ion values (L <= 12 * 512: the configurations' 3001 / 6002 frames) are requested first, so
   // their loads are in flight together with the mem partials' instead of after them
   constexpr int IQ = 6144 / CT;
@@ -46,7 +71,11 @@ __global__ __launch_bounds__(CT) void msheath_ctrl_fwd_kernel(
   float iv[IQ];
   if (ion_pre) {
 #pragma unroll
-    for (int j = 0; j < IQ; ++j) iv[j] = ib[min<int64_t>(threadIdx.x + CT * j, L - 1)];
+    for (int j = 0; j < IQ; ++j) {
+      // (LENS: clamped to the sample's last live row, row 0 of an empty one)
+      if constexpr (LENS) iv[j] = ib[min<int64_t>(threadIdx.x + CT * j, Lb > 0 ? Lb - 1 : (int64_t)0)];
+      else iv[j] = ib[min<int64_t>(threadIdx.x + CT * j, L - 1)];
+    }
   }
   if (mem_part) {  // mem = (1/L) sum over the row chunks of x_new, in chunk order (deterministic)
     // the chunk partials are loaded 16 at a time before they are added (in chunk order, so the sum
@@ -61,23 +90,29 @@ __global__ __launch_bounds__(CT) void msheath_ctrl_fwd_kernel(
       const bool two = c1 < D;
       const int c1c = two ? c1 : c0;
       float t0 = 0.f, t1 = 0.f;
-      for (int k = 0; k < nchunk; k += 16) {
+      for (int k = 0; k < ncb; k += 16) {
         float v0[16], v1[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-          const int64_t kk = min(k + j, nchunk - 1);
+          const int64_t kk = min(k + j, ncb - 1);
           v0[j] = mp[kk * D + c0];
           v1[j] = mp[kk * D + c1c];
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j)
-          if (k + j < nchunk) {
+          if (k + j < ncb) {
             t0 += v0[j];
             t1 += v1[j];
           }
       }
-      mem_out[b * D + c0] = t0 * (1.0f / (float)L);
-      if (two) mem_out[b * D + c1] = t1 * (1.0f / (float)L);
+      if constexpr (LENS) {
+        const float rl = seq_rcp((int)Lb);
+        mem_out[b * D + c0] = t0 * rl;
+        if (two) mem_out[b * D + c1] = t1 * rl;
+      } else {
+        mem_out[b * D + c0] = t0 * (1.0f / (float)L);
+        if (two) mem_out[b * D + c1] = t1 * (1.0f / (float)L);
+      }
     }
     __syncthreads();
     mem = mem_out;
@@ -86,18 +121,24 @@ __global__ __launch_bounds__(CT) void msheath_ctrl_fwd_kernel(
   if (ion_pre) {  // the thread's values in the order of the loop below
 #pragma unroll
     for (int j = 0; j < IQ; ++j)
-      if (threadIdx.x + CT * j < L) s += iv[j];
+      if (threadIdx.x + CT * j < Lb) s += iv[j];
   } else {
-    for (int64_t l = threadIdx.x; l < L; l += 8 * CT) {  // 8 loads in flight (the tail's from clamped
-      float v[8];                                          // addresses), added in the same order
+    for (int64_t l = threadIdx.x; l < Lb; l += 8 * CT) {  // 8 loads in flight (the tail's from clamped
+      float v[8];                                           // addresses), added in the same order
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = ib[min<int64_t>(l + CT * j, L - 1)];
+      for (int j = 0; j < 8; ++j) v[j] = ib[min<int64_t>(l + CT * j, Lb - 1)];
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        if (l + CT * j < L) s += v[j];
+        if (l + CT * j < Lb) s += v[j];
     }
   }
-  const float potential = block_sum<CT>(s, red) / (float)L;  // ion.mean(dim=1), model.py:466
+  float potential;  // ion.mean(dim=1), model.py:466
+  if constexpr (LENS) {
+    const float t = block_sum<CT>(s, red);
+    potential = Lb > 0 ? t / (float)Lb : 0.f;
+  } else {
+    potential = block_sum<CT>(s, red) / (float)L;
+  }
   float mv;
   if (mg_w) {  // mem_v = sigmoid(mem_gate(mem)) computed here (model.py:464)
     float t = 0.f;
@@ -169,6 +210,8 @@ __global__ __launch_bounds__(CT) void msheath_ctrl_fwd_kernel(
 
 // Backward.  g_mwo may be null (mem_w of the last layer is not used).  Writes g_policy (B,3),
 // g_mem_v (B), g_mem_w (B,D), g_mem (B,D); accumulates g_jump_s (3) with atomics.
+// LENS: the first ceil(T_b / 128) L-chunks of part_ab and part_g are added (the chunks that hold live rows).
+template <bool LENS = false>
 __global__ __launch_bounds__(256) void msheath_ctrl_bwd_kernel(
     const float* __restrict__ g_alpha, const float* __restrict__ g_beta, const float* __restrict__ g_gam,
     const float* __restrict__ g_mwo, const float* __restrict__ mem_v, const float* __restrict__ mem_w,
@@ -177,9 +220,11 @@ __global__ __launch_bounds__(256) void msheath_ctrl_bwd_kernel(
     float* __restrict__ g_mem, float* __restrict__ g_jump_s, int64_t ld_mem_w, int* __restrict__ has_orig,
     int acc_policy, const float* __restrict__ mg_w, float* __restrict__ g_mg_w, float* __restrict__ g_mg_b,
     const float2* __restrict__ part_ab = nullptr, const float* __restrict__ part_g = nullptr, int nlc = 0,
-    int ncc = 0) {
+    int ncc = 0, const int32_t* __restrict__ lens = nullptr, int L = 0) {
   __shared__ float red[4];
   const int64_t b = blockIdx.x;
+  int nlb = nlc;  // the L-chunks added (nlc stays the slot stride)
+  if constexpr (LENS) nlb = (seq_len(lens, b, L) + JUMP_CHUNK - 1) / JUMP_CHUNK;
   const CtrlRec r = rec[b];
   const float mv = mem_v[b];
   const bool act = r.act != 0.f;
@@ -190,13 +235,13 @@ __global__ __launch_bounds__(256) void msheath_ctrl_bwd_kernel(
     float gg;
     if (part_g) {  // the jump-select backward's L-chunk partials, added in chunk order (deterministic;
       gg = 0.f;      // 16 loads in flight, the last group's from clamped addresses)
-      for (int k = 0; k < nlc; k += 16) {
+      for (int k = 0; k < nlb; k += 16) {
         float v[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = part_g[(b * nlc + min(k + j, nlc - 1)) * D + c];
+        for (int j = 0; j < 16; ++j) v[j] = part_g[(b * nlc + min(k + j, nlb - 1)) * D + c];
 #pragma unroll
         for (int j = 0; j < 16; ++j)
-          if (k + j < nlc) gg += v[j];
+          if (k + j < nlb) gg += v[j];
       }
     } else {
       gg = g_gam[b * D + c];
@@ -225,8 +270,8 @@ __global__ __launch_bounds__(256) void msheath_ctrl_bwd_kernel(
     float ga, gb;
     if (part_ab) {  // in order, 16 loads in flight (a dependent chain of ~100 loads cost ~10 us per launch)
       ga = 0.f, gb = 0.f;
-      const int n = nlc * ncc;
-      const float2* pb = part_ab + b * n;
+      const int n = nlb * ncc;
+      const float2* pb = part_ab + b * (nlc * ncc);
       for (int k = 0; k < n; k += 16) {
         float2 v[16];
 #pragma unroll
@@ -277,12 +322,14 @@ __global__ void axpy_row2_kernel(const float4* __restrict__ x, const float* __re
 // (d4 <= 256), each keeping its column's partial sum in registers; the workgroup's sums go to
 // part[b][chunk][:] (no atomics: the control kernel adds the chunks in a fixed order, so the forward
 // is deterministic -- its hard decisions must not depend on atomic ordering).
-constexpr int MEM_CHUNK = 64;
+// LENS: a chunk's rows stop at T_b (one with no live row stores a zero partial, like a sample not at the layer),
+// and the chunk's pad rows of out are stored as zeros.
+template <bool LENS = false>
 __global__ __launch_bounds__(256) void axpy_row2_colsum_kernel(const float4* __restrict__ x, const float* __restrict__ s1,
                                                                const float* __restrict__ s2, const float4* __restrict__ y,
                                                                float4* __restrict__ out, float4* __restrict__ part,
                                                                int64_t L, int d4, const float* __restrict__ next_i,
-                                                               int layer) {
+                                                               int layer, const int32_t* __restrict__ lens = nullptr) {
   __shared__ float4 red[256];
   const int nrl = 256 / d4;
   const int c = threadIdx.x % d4, rl = threadIdx.x / d4;
@@ -291,7 +338,9 @@ __global__ __launch_bounds__(256) void axpy_row2_colsum_kernel(const float4* __r
     if (rl == 0) part[((int64_t)b * gridDim.y + blockIdx.y) * d4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
-  const int64_t l0 = (int64_t)blockIdx.y * MEM_CHUNK, l1 = min<int64_t>(L, l0 + MEM_CHUNK);
+  int64_t Lb = L;
+  if constexpr (LENS) Lb = seq_len(lens, b, (int)L);
+  const int64_t l0 = (int64_t)blockIdx.y * MEM_CHUNK, l1 = min<int64_t>(Lb, l0 + MEM_CHUNK);
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   auto one = [&](float sc, float4 a, float4 v, int64_t i) __attribute__((always_inline)) {
     const float4 o = make_float4(__builtin_fmaf(sc, v.x, a.x), __builtin_fmaf(sc, v.y, a.y),
@@ -325,6 +374,11 @@ __global__ __launch_bounds__(256) void axpy_row2_colsum_kernel(const float4* __r
     for (; l < l1; l += nrl) {
       const int64_t r = b * L + l;
       one(s1[r] * s2[r], x[r * d4 + c], y[r * d4 + c], r * d4 + c);
+    }
+    if constexpr (LENS) {
+      if (out)
+        for (l = max(l1, l0) + rl; l < min<int64_t>(L, l0 + MEM_CHUNK); l += nrl)
+          out[(b * L + l) * d4 + c] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   red[threadIdx.x] = acc;
@@ -362,16 +416,27 @@ __global__ __launch_bounds__(256) void axpy_row2_bwd_kernel(const float4* __rest
 }
 
 // jump_select forward, float4: out = act ? alpha*xn + beta*orig + gam : xold.  grid (chunks, B).
+// LENS: rows at or past T_b are stored as zeros and nothing of them is read.
+template <bool LENS = false>
 __global__ void jump_select4_kernel(const float4* __restrict__ xn, const float4* __restrict__ orig,
                                     const float4* __restrict__ xold, const float* __restrict__ act,
                                     const float* __restrict__ alpha, const float* __restrict__ beta,
-                                    const float4* __restrict__ gam, float4* __restrict__ out, int64_t L, int d4) {
+                                    const float4* __restrict__ gam, float4* __restrict__ out, int64_t L, int d4,
+                                    const int32_t* __restrict__ lens = nullptr) {
   const int64_t b = blockIdx.y;
   const int64_t n = L * d4;
   const int64_t base = b * n;
   const bool a = act[b] != 0.f;
   const float al = alpha[b], be = beta[b];
+  int64_t nl = n;
+  if constexpr (LENS) nl = (int64_t)seq_len(lens, b, (int)L) * d4;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (LENS) {
+      if (i >= nl) {
+        out[base + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+    }
     if (a) {
       const float4 u = xn[base + i], v = orig[base + i], w = gam[b * d4 + i % d4];
       out[base + i] = make_float4(__builtin_fmaf(al, u.x, __builtin_fmaf(be, v.x, w.x)),
@@ -389,22 +454,40 @@ __global__ void jump_select4_kernel(const float4* __restrict__ xn, const float4*
 // (model.py:461) and the jump select (489-501) in one pass without materialising x_new.  In place
 // (xin == xout) a sample not at the layer is not touched -- its x already is the layer's output; otherwise
 // it is copied.  Same arithmetic as axpy_row2_colsum + jump_select4 (explicit fma): bit-identical.
+// LENS: rows at or past T_b are not read; out of place they are stored as zeros, in place they hold zeros already.
+template <bool LENS = false>
 __global__ void jump_axpy_inplace_kernel(const float4* xin, float4* xout, const float* __restrict__ s1,
                                          const float* __restrict__ s2, const float4* __restrict__ y,
                                          const float4* __restrict__ orig, const float* __restrict__ act,
                                          const float* __restrict__ alpha, const float* __restrict__ beta,
-                                         const float4* __restrict__ gam, int64_t L, int d4) {
+                                         const float4* __restrict__ gam, int64_t L, int d4,
+                                         const int32_t* __restrict__ lens = nullptr) {
   const int64_t b = blockIdx.y;
   const int64_t n = L * d4;
   const int64_t base = b * n;
+  int64_t nl = n;
+  if constexpr (LENS) nl = (int64_t)seq_len(lens, b, (int)L) * d4;
   if (act[b] == 0.f) {
     if (xin != xout)
-      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if constexpr (LENS) {
+          if (i >= nl) {
+            xout[base + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+          }
+        }
         xout[base + i] = xin[base + i];
+      }
     return;
   }
   const float al = alpha[b], be = beta[b];
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (LENS) {
+      if (i >= nl) {
+        if (xin != xout) xout[base + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+    }
     const int64_t r = b * L + i / d4;
     const float sc = s1[r] * s2[r];
     const float4 a = xin[base + i], v = y[base + i], o = orig[base + i], w = gam[b * d4 + i % d4];
@@ -494,6 +577,7 @@ __global__ __launch_bounds__(256) void jump_select4_bwd_kernel(
 // dorig (+)= beta g only when beta != 0 (a jump), the first jumping layer of a sample writing
 // (has_orig[b] == 0, set afterwards by msheath_ctrl_bwd); x_i's gradient is left to
 // axpy_row2_bwd_acc.  Inactive samples: dx = g (the pass-through), nothing else.
+// (jump_select4_bwd_part_lens_kernel below is a copy of the partial form with per-sample lengths: keep them in step.)
 __global__ __launch_bounds__(256) void jump_select4_bwd_acc_kernel(
     const float4* __restrict__ g, const float4* __restrict__ xn, const float4* __restrict__ orig,
     const float* __restrict__ act, const float* __restrict__ alpha, const float* __restrict__ beta,
@@ -574,12 +658,103 @@ __global__ __launch_bounds__(256) void jump_select4_bwd_acc_kernel(
   }
 }
 
+// The partial form of jump_select4_bwd_acc_kernel with per-sample lengths (asrx_jump_lens_select4_bwd_part2), a
+// kernel of its own so that the uniform one above keeps its code: a template's two LDS arrays are laid out in another
+// order than a plain function's.  KEEP THE TWO IN STEP: a change to the row loop, the sums or their order above
+// belongs here too (tests/test_gpu_msheath_lens.py test_jump_partials_and_ctrl_bwd compares the two bit for bit).
+// Same grid, row groups, sums and order; the rows stop at T_b, pad rows of g are not read, and the pad rows of what
+// this pass is the first writer of (dxn, a first jump's dorig, an inactive sample's dx) are stored as zeros.  Every
+// (sample, L chunk, column chunk) partial slot is written, zeros where nothing is live.
+__global__ __launch_bounds__(256) void jump_select4_bwd_part_lens_kernel(
+    const float4* __restrict__ g, const float4* __restrict__ xn, const float4* __restrict__ orig,
+    const float* __restrict__ act, const float* __restrict__ alpha, const float* __restrict__ beta,
+    const int* __restrict__ has_orig, float4* __restrict__ dxn, float4* __restrict__ dorig, float4* __restrict__ dx,
+    int64_t L, int d4, int lchunk, float2* __restrict__ part_ab, float* __restrict__ part_g,
+    const int32_t* __restrict__ lens) {
+  __shared__ float4 sg_s[8][32];
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  const int cchunks = (d4 + 31) / 32;
+  const int cc = blockIdx.x % cchunks;
+  const int lc = blockIdx.x / cchunks, nlc = gridDim.x / cchunks;
+  const int64_t b = blockIdx.y;
+  const int64_t Lb = seq_len(lens, b, (int)L);
+  const int64_t l0 = (int64_t)lc * lchunk;
+  const int64_t l1 = min(Lb, l0 + lchunk);
+  const int c4 = cc * 32 + lane;
+  const bool a = act[b] != 0.f;
+  const float al = alpha[b], be = beta[b];
+  const bool jo = be != 0.f, acc_o = has_orig[b] != 0;
+  float sa = 0.f, sb = 0.f;
+  float4 sgv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c4 < d4) {
+    for (int64_t l = l0 + grp; l < l1; l += 8) {
+      const int64_t i = (b * L + l) * d4 + c4;
+      const float4 gv = g[i];
+      if (a) {
+        const float4 u = xn[i], v = orig[i];
+        sa += gv.x * u.x + gv.y * u.y + gv.z * u.z + gv.w * u.w;
+        sb += gv.x * v.x + gv.y * v.y + gv.z * v.z + gv.w * v.w;
+        sgv.x += gv.x; sgv.y += gv.y; sgv.z += gv.z; sgv.w += gv.w;
+        if (dxn) dxn[i] = make_float4(al * gv.x, al * gv.y, al * gv.z, al * gv.w);
+        if (jo) {
+          float4 o = make_float4(be * gv.x, be * gv.y, be * gv.z, be * gv.w);
+          if (acc_o) {
+            const float4 p = dorig[i];
+            o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w;
+          }
+          dorig[i] = o;
+        }
+      } else {
+        dx[i] = gv;
+      }
+    }
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t l = max(l1, l0) + grp; l < min(L, l0 + lchunk); l += 8) {  // the chunk's pad rows
+      const int64_t i = (b * L + l) * d4 + c4;
+      if (a) {
+        if (dxn) dxn[i] = z4;
+        if (jo && !acc_o) dorig[i] = z4;
+      } else {
+        dx[i] = z4;
+      }
+    }
+  }
+  sg_s[grp][lane] = sgv;
+  sa = wave_sum(sa);
+  sb = wave_sum(sb);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = sa;
+    red[1][threadIdx.x >> 6] = sb;
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int cl = threadIdx.x >> 2, q = threadIdx.x & 3;
+    const int c4b = cc * 32 + cl;
+    if (c4b < d4) {
+      float t = 0.f;
+      for (int g2 = 0; g2 < 8; ++g2) {
+        const float4 v = sg_s[g2][cl];
+        t += q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w;
+      }
+      part_g[(b * nlc + lc) * 4 * d4 + 4 * c4b + q] = t;
+    }
+  } else if (threadIdx.x == 128) {
+    const float A = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    const float Bv = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    part_ab[(b * nlc + lc) * cchunks + cc] = make_float2(A, Bv);
+  }
+}
+
 // x_new = x + s1 s2 y (model.py:461) and mem = mean_l x_new (model.py:463) backward, for active
 // samples: g' = dxn + gm[b] / L (the seg-mean broadcast folded in), dy = s1 s2 g', ds1 = s2 g'.y,
 // ds2 = s1 g'.y, and dx = g' -- the first contribution to x_i of an active sample.  Inactive
 // samples: dy = 0, ds = 0, dx untouched (jump_select4_bwd_acc wrote the pass-through).
 // alpha non-null: dxn is the jump's incoming gradient g and dxn = alpha[b] g is formed here (the same product
 // jump_select4_bwd_acc would have stored).
+// LENS: invL is 1 / T_b of the row's sample; a pad row reads nothing and gets dy = 0, ds = 0 and, for an active
+// sample (whose dx this pass writes first), dx = 0.
+template <bool LENS = false>
 __global__ __launch_bounds__(256) void axpy_row2_bwd_acc_kernel(const float4* __restrict__ dxn,
                                                                 const float* __restrict__ gm, float invL,
                                                                 const float* __restrict__ act,
@@ -587,11 +762,27 @@ __global__ __launch_bounds__(256) void axpy_row2_bwd_acc_kernel(const float4* __
                                                                 const float4* __restrict__ y, float4* __restrict__ dy,
                                                                 float* __restrict__ ds1, float* __restrict__ ds2,
                                                                 float4* __restrict__ dx, int64_t rows, int64_t L, int d4,
-                                                                const float* __restrict__ alpha = nullptr) {
+                                                                const float* __restrict__ alpha = nullptr,
+                                                                const int32_t* __restrict__ lens = nullptr) {
   const int lane = threadIdx.x & 63;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += (int64_t)gridDim.x * 4) {
     const int64_t b = r / L;
+    if constexpr (LENS) {
+      const int Tb = seq_len(lens, b, (int)L);
+      invL = seq_rcp(Tb);
+      if (act[b] != 0.f && r - b * L >= Tb) {
+        for (int j = lane; j < d4; j += 64) {
+          dy[r * d4 + j] = z4;
+          dx[r * d4 + j] = z4;
+        }
+        if (lane == 0) {
+          ds1[r] = 0.f;
+          if (ds2) ds2[r] = 0.f;
+        }
+        continue;
+      }
+    }
     if (act[b] == 0.f) {
       for (int j = lane; j < d4; j += 64) dy[r * d4 + j] = z4;
       if (lane == 0) {
@@ -627,15 +818,28 @@ __global__ __launch_bounds__(256) void axpy_row2_bwd_acc_kernel(const float4* __
 
 // dx += (has_orig[b] ? dorig : 0) + u[b, :]   (orig's jump gradient and the pooled-mean broadcast of
 // the MSheath input, model.py:432-435, 497)
+// LENS: u is dpooled and the broadcast is u[b, :] (1 / T_b), the product rounded on its own as asrx_lincomb stores it
+// (this unit builds without contractions); pad rows of dx are stored as zeros and dorig is not read there.
+template <bool LENS = false>
 __global__ void msheath_dx_final_kernel(float4* __restrict__ dx, const float4* __restrict__ dorig,
                                         const int* __restrict__ has_orig, const float4* __restrict__ u, int64_t B,
-                                        int64_t L, int d4) {
+                                        int64_t L, int d4, const int32_t* __restrict__ lens = nullptr) {
   const int64_t total = B * L * d4;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t b = i / (L * d4);
+    float rl = 1.f;
+    if constexpr (LENS) {
+      const int Tb = seq_len(lens, b, (int)L);
+      if (i - b * (L * d4) >= (int64_t)Tb * d4) {
+        dx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+      rl = seq_rcp(Tb);
+    }
     float4 v = dx[i];
     if (u) {
-      const float4 w = u[b * d4 + i % d4];
+      float4 w = u[b * d4 + i % d4];
+      if constexpr (LENS) w = make_float4(rl * w.x, rl * w.y, rl * w.z, rl * w.w);
       v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
     }
     if (has_orig[b]) {
@@ -652,10 +856,10 @@ using namespace asrx;
 
 
 // the forward control kernel at its thread count for D (CT above)
-template <typename... A>
+template <bool LENS = false, typename... A>
 static void ctrl_fwd_launch(int64_t D, int64_t B, hipStream_t stream, A... a) {
-  if (D > 512) msheath_ctrl_fwd_kernel<512><<<(unsigned)B, 512, 0, stream>>>(a...);
-  else msheath_ctrl_fwd_kernel<256><<<(unsigned)B, 256, 0, stream>>>(a...);
+  if (D > 512) msheath_ctrl_fwd_kernel<512, LENS><<<(unsigned)B, 512, 0, stream>>>(a...);
+  else msheath_ctrl_fwd_kernel<256, LENS><<<(unsigned)B, 256, 0, stream>>>(a...);
 }
 
 extern "C" {
@@ -732,7 +936,7 @@ int asrx_axpy_row2_bwd_acc(const float* dxn, const float* gm, float invL, const 
   ASRX_REQUIRE(d % 4 == 0, "asrx_axpy_row2_bwd_acc: d % 4 != 0");
   const int64_t rows = B * L;
   if (rows == 0) return 0;
-  axpy_row2_bwd_acc_kernel<<<(unsigned)std::min<int64_t>((rows + 3) / 4, 8192), 256, 0, stream>>>(
+  axpy_row2_bwd_acc_kernel<false><<<(unsigned)std::min<int64_t>((rows + 3) / 4, 8192), 256, 0, stream>>>(
       (const float4*)dxn, gm, invL, act, s1, s2, (const float4*)y, (float4*)dy, ds1, ds2, (float4*)dx, rows, L,
       (int)(d / 4));
   ASRX_LAUNCHED("asrx_axpy_row2_bwd_acc");
@@ -748,7 +952,7 @@ int asrx_axpy_row2_bwd_acc2(const float* g, const float* alpha, const float* gm,
   ASRX_REQUIRE(alpha && dx, "asrx_axpy_row2_bwd_acc2: alpha and dx required");
   const int64_t rows = B * L;
   if (rows == 0) return 0;
-  axpy_row2_bwd_acc_kernel<<<(unsigned)std::min<int64_t>((rows + 3) / 4, 8192), 256, 0, stream>>>(
+  axpy_row2_bwd_acc_kernel<false><<<(unsigned)std::min<int64_t>((rows + 3) / 4, 8192), 256, 0, stream>>>(
       (const float4*)g, gm, invL, act, s1, s2, (const float4*)y, (float4*)dy, ds1, ds2, (float4*)dx, rows, L,
       (int)(d / 4), alpha);
   ASRX_LAUNCHED("asrx_axpy_row2_bwd_acc2");
@@ -759,7 +963,7 @@ int asrx_msheath_dx_final(float* dx, const float* dorig, const int* has_orig, co
   ASRX_REQUIRE(d % 4 == 0, "asrx_msheath_dx_final: d % 4 != 0");
   if (B * L == 0) return 0;
   const int64_t n = B * L * d / 4;
-  msheath_dx_final_kernel<<<(unsigned)std::min<int64_t>((n + 255) / 256, 16384), 256, 0, stream>>>(
+  msheath_dx_final_kernel<false><<<(unsigned)std::min<int64_t>((n + 255) / 256, 16384), 256, 0, stream>>>(
       (float4*)dx, (const float4*)dorig, has_orig, (const float4*)u, B, L, (int)(d / 4));
   ASRX_LAUNCHED("asrx_msheath_dx_final");
 }
@@ -815,7 +1019,8 @@ int asrx_msheath_ctrl_bwd(const float* g_alpha, const float* g_beta, const float
                           const void* rec, int64_t layer_i, int64_t layers, int64_t B, int64_t D, float* g_policy,
                           float* g_mem_v, float* g_mem_w, float* g_mem, float* g_jump_s, hipStream_t stream) {
   if (B == 0) return 0;
-  msheath_ctrl_bwd_kernel<<<(unsigned)B, 256, 0, stream>>>(g_alpha, g_beta, g_gam, g_mwo, mem_v, mem_w, mem, jump_s,
+  msheath_ctrl_bwd_kernel<false><<<(unsigned)B, 256, 0, stream>>>(g_alpha, g_beta, g_gam, g_mwo, mem_v, mem_w, mem,
+                                                                  jump_s,
                                                            (const CtrlRec*)rec, (int)layer_i, (int)layers, (int)D,
                                                            g_policy, g_mem_v, g_mem_w, g_mem, g_jump_s, D, nullptr, 0,
                                                            nullptr, nullptr, nullptr);
@@ -830,7 +1035,8 @@ int asrx_msheath_ctrl_bwd2(const float* g_alpha, const float* g_beta, const floa
                            float* g_policy, int acc_policy, float* g_mem_v, float* g_mem_w, float* g_mem,
                            float* g_jump_s, int* has_orig, hipStream_t stream) {
   if (B == 0) return 0;
-  msheath_ctrl_bwd_kernel<<<(unsigned)B, 256, 0, stream>>>(g_alpha, g_beta, g_gam, g_mwo, mem_v, mem_w, mem, jump_s,
+  msheath_ctrl_bwd_kernel<false><<<(unsigned)B, 256, 0, stream>>>(g_alpha, g_beta, g_gam, g_mwo, mem_v, mem_w, mem,
+                                                                  jump_s,
                                                            (const CtrlRec*)rec, (int)layer_i, (int)layers, (int)D,
                                                            g_policy, g_mem_v, g_mem_w, g_mem, g_jump_s, ld_mem_w,
                                                            has_orig, acc_policy, nullptr, nullptr, nullptr);
@@ -845,7 +1051,8 @@ int asrx_msheath_ctrl_bwd3(const float* g_alpha, const float* g_beta, const floa
                            float* g_policy, int acc_policy, float* g_mem_w, float* g_mem, float* g_jump_s,
                            int* has_orig, const float* mg_w, float* g_mg_w, float* g_mg_b, hipStream_t stream) {
   if (B == 0) return 0;
-  msheath_ctrl_bwd_kernel<<<(unsigned)B, 256, 0, stream>>>(g_alpha, g_beta, g_gam, g_mwo, mem_v, mem_w, mem, jump_s,
+  msheath_ctrl_bwd_kernel<false><<<(unsigned)B, 256, 0, stream>>>(g_alpha, g_beta, g_gam, g_mwo, mem_v, mem_w, mem,
+                                                                  jump_s,
                                                            (const CtrlRec*)rec, (int)layer_i, (int)layers, (int)D,
                                                            g_policy, nullptr, g_mem_w, g_mem, g_jump_s, ld_mem_w,
                                                            has_orig, acc_policy, mg_w, g_mg_w, g_mg_b);
@@ -864,7 +1071,7 @@ int asrx_msheath_ctrl_bwd4(const float* part, int64_t L, const float* g_mwo, con
   const int64_t nlc = (L + 127) / 128, ncc = (D / 4 + 31) / 32;
   const float2* part_ab = reinterpret_cast<const float2*>(part);
   const float* part_g = part + 2 * B * nlc * ncc;
-  msheath_ctrl_bwd_kernel<<<(unsigned)B, 256, 0, stream>>>(nullptr, nullptr, nullptr, g_mwo, mem_v, mem_w, mem,
+  msheath_ctrl_bwd_kernel<false><<<(unsigned)B, 256, 0, stream>>>(nullptr, nullptr, nullptr, g_mwo, mem_v, mem_w, mem,
                                                            jump_s, (const CtrlRec*)rec, (int)layer_i, (int)layers,
                                                            (int)D, g_policy, nullptr, g_mem_w, g_mem, g_jump_s,
                                                            ld_mem_w, has_orig, acc_policy, mg_w, g_mg_w, g_mg_b,
@@ -881,7 +1088,7 @@ int asrx_axpy_row2_colsum(const float* x, const float* s1, const float* s2, cons
   if (B * L == 0) return 0;
   const int d4 = (int)(d / 4);
   dim3 grid((unsigned)B, (unsigned)asrx_mem_chunks(L));
-  axpy_row2_colsum_kernel<<<grid, 256, 0, stream>>>((const float4*)x, s1, s2, (const float4*)y, (float4*)out,
+  axpy_row2_colsum_kernel<false><<<grid, 256, 0, stream>>>((const float4*)x, s1, s2, (const float4*)y, (float4*)out,
                                                     (float4*)part, L, d4, next_i, (int)layer);
   ASRX_LAUNCHED("asrx_axpy_row2_colsum");
 }
@@ -916,7 +1123,7 @@ int asrx_jump_axpy_inplace(const float* xin, float* xout, const float* s1, const
   ASRX_REQUIRE(d / 4 <= 256, "asrx_jump_axpy_inplace: d <= 1024 required");
   // flat grid-stride (measured faster than 64- or 16-row chunk grids: profiles/r04_jump_ab.txt)
   dim3 grid((unsigned)std::min<int64_t>((L * (d / 4) + 255) / 256, 512), (unsigned)B);
-  jump_axpy_inplace_kernel<<<grid, 256, 0, stream>>>((const float4*)xin, (float4*)xout, s1, s2, (const float4*)y,
+  jump_axpy_inplace_kernel<false><<<grid, 256, 0, stream>>>((const float4*)xin, (float4*)xout, s1, s2, (const float4*)y,
                                                      (const float4*)orig, act, alpha, beta, (const float4*)gam, L,
                                                      (int)(d / 4));
   ASRX_LAUNCHED("asrx_jump_axpy_inplace");
@@ -929,7 +1136,7 @@ int asrx_jump_select4(const float* xn, const float* orig, const float* xold, con
   if (B * L == 0) return 0;
   // flat grid-stride (measured faster than 64- or 16-row chunk grids: profiles/r04_jump_ab.txt)
   dim3 grid((unsigned)std::min<int64_t>((L * (d / 4) + 255) / 256, 512), (unsigned)B);
-  jump_select4_kernel<<<grid, 256, 0, stream>>>((const float4*)xn, (const float4*)orig, (const float4*)xold, act,
+  jump_select4_kernel<false><<<grid, 256, 0, stream>>>((const float4*)xn, (const float4*)orig, (const float4*)xold, act,
                                                 alpha, beta, (const float4*)gam, (float4*)out, L, (int)(d / 4));
   ASRX_LAUNCHED("asrx_jump_select4");
 }
@@ -950,5 +1157,160 @@ int asrx_jump_select4_bwd(const float* g, const float* xn, const float* orig, co
                                                     dbeta, dgam, L, d4, lchunk);
   ASRX_LAUNCHED("asrx_jump_select4_bwd");
 }
+
+// ---- MSheath with per-sample lengths: the LENS instantiations.  `lens` is a device table of B int32
+// (asrx_act_lens_fwd's), T_b = lens[b] clamped to [0, L].  Each entry point is its uniform twin with `lens` ahead of
+// the sizes; it gives the twin's refusals in the twin's words and keeps its early return in place, then refuses a null
+// and a misaligned table.  The reciprocals the twins take as arguments (invL, the scale of u) are 1 / T_b, formed on
+// the device.
+#define ASRX_REQUIRE_LENS(name)                                                                 \
+  ASRX_REQUIRE(lens != nullptr, name ": per-sample lengths: null table");                       \
+  ASRX_REQUIRE(((uintptr_t)lens & 3) == 0, name ": per-sample lengths: table must be 4-byte aligned")
+
+// asrx_jump_select4_bwd_part2 with lengths (dxn may be null)
+int asrx_jump_lens_select4_bwd_part2(const float* g, const float* xn, const float* orig, const float* act,
+                                     const float* alpha, const float* beta, const int* has_orig, float* dxn,
+                                     float* dorig, float* dx, float* part, const int32_t* lens, int64_t B, int64_t L,
+                                     int64_t d, hipStream_t stream) {
+  ASRX_REQUIRE(d % 4 == 0, "asrx_jump_select4_bwd_part: d % 4 != 0");
+  if (B * L == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_jump_lens_select4_bwd_part2: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_jump_lens_select4_bwd_part2");
+  const int d4 = (int)(d / 4);
+  const int lchunk = JUMP_CHUNK;
+  const int64_t nlc = (L + lchunk - 1) / lchunk, ncc = (d4 + 31) / 32;
+  float2* part_ab = reinterpret_cast<float2*>(part);
+  float* part_g = part + 2 * B * nlc * ncc;
+  dim3 grid((unsigned)(ncc * nlc), (unsigned)B);
+  jump_select4_bwd_part_lens_kernel<<<grid, 256, 0, stream>>>((const float4*)g, (const float4*)xn, (const float4*)orig,
+                                                              act, alpha, beta, has_orig, (float4*)dxn, (float4*)dorig,
+                                                              (float4*)dx, L, d4, lchunk, part_ab, part_g, lens);
+  ASRX_LAUNCHED("asrx_jump_lens_select4_bwd_part2");
+}
+
+// asrx_axpy_row2_bwd_acc (alpha null) and asrx_axpy_row2_bwd_acc2 (alpha given) with lengths: g' = [alpha] g + gm / T_b
+int asrx_axpy_row2_lens_bwd_acc2(const float* g, const float* alpha, const float* gm, const float* act,
+                                 const float* s1, const float* s2, const float* y, float* dy, float* ds1, float* ds2,
+                                 float* dx, const int32_t* lens, int64_t B, int64_t L, int64_t d,
+                                 hipStream_t stream) {
+  // (the twin's words: asrx_axpy_row2_bwd_acc2 with alpha, asrx_axpy_row2_bwd_acc without)
+  ASRX_REQUIRE(d % 4 == 0, alpha ? "asrx_axpy_row2_bwd_acc2: d % 4 != 0" : "asrx_axpy_row2_bwd_acc: d % 4 != 0");
+  ASRX_REQUIRE(dx, "asrx_axpy_row2_lens_bwd_acc2: dx required");
+  const int64_t rows = B * L;
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_axpy_row2_lens_bwd_acc2: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_axpy_row2_lens_bwd_acc2");
+  axpy_row2_bwd_acc_kernel<true><<<(unsigned)std::min<int64_t>((rows + 3) / 4, 8192), 256, 0, stream>>>(
+      (const float4*)g, gm, 0.f, act, s1, s2, (const float4*)y, (float4*)dy, ds1, ds2, (float4*)dx, rows, L,
+      (int)(d / 4), alpha, lens);
+  ASRX_LAUNCHED("asrx_axpy_row2_lens_bwd_acc2");
+}
+
+// asrx_msheath_dx_final with lengths, taking dpooled (B, d) itself:
+// dx += (has_orig[b] ? dorig : 0) + dpooled[b, :] / T_b
+// on live rows (asrx_lincomb's product, then the twin's adds); pad rows of dx are stored as zeros
+int asrx_msheath_lens_dx_final(float* dx, const float* dorig, const int* has_orig, const float* dpooled,
+                               const int32_t* lens, int64_t B, int64_t L, int64_t d, hipStream_t stream) {
+  ASRX_REQUIRE(d % 4 == 0, "asrx_msheath_dx_final: d % 4 != 0");
+  if (B * L == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_msheath_lens_dx_final: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_msheath_lens_dx_final");
+  const int64_t n = B * L * d / 4;
+  msheath_dx_final_kernel<true><<<(unsigned)std::min<int64_t>((n + 255) / 256, 16384), 256, 0, stream>>>(
+      (float4*)dx, (const float4*)dorig, has_orig, (const float4*)dpooled, B, L, (int)(d / 4), lens);
+  ASRX_LAUNCHED("asrx_msheath_lens_dx_final");
+}
+
+// asrx_msheath_ctrl_fwd3 with lengths: mem = (1 / T_b) sum of the first ceil(T_b / 64) chunk partials, potential =
+// (sum of ion rows below T_b) / T_b; both 0 for T_b = 0
+int asrx_msheath_ctrl_lens_fwd3(const float* policy, const float* gpol, int64_t ld_gpol, const float* ion,
+                                const float* mg_w, const float* mg_b, float* mem_v_out, const float* mem_w,
+                                int64_t ld_mem_w, const float* mem_part, float* mem, const float* jump_s,
+                                const float* next_i, int64_t layer_i, int64_t layers, const int32_t* lens, int64_t B,
+                                int64_t L, int64_t D, float* alpha, float* beta, float* gam, float* mem_w_out,
+                                float* active, float* next_out, void* rec, hipStream_t stream) {
+  if (B == 0) return 0;
+  ASRX_REQUIRE(L > 0 && L < (1LL << 31), "asrx_msheath_ctrl_lens_fwd3: 0 < L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_msheath_ctrl_lens_fwd3");
+  const int nchunk = (int)((L + MEM_CHUNK - 1) / MEM_CHUNK);
+  ctrl_fwd_launch<true>(D, B, stream, policy, gpol, ld_gpol, ion, nullptr, mem_w, mem, jump_s, next_i, (int)layer_i,
+                        (int)layers, L, (int)D, alpha, beta, gam, mem_w_out, active, next_out, (CtrlRec*)rec, ld_mem_w,
+                        mg_w, mg_b, mem_v_out, mem_part, nchunk, mem, lens);
+  ASRX_LAUNCHED("asrx_msheath_ctrl_lens_fwd3");
+}
+
+// asrx_msheath_ctrl_bwd4 with lengths: the first ceil(T_b / 128) L-chunks of the partials of
+// asrx_jump_lens_select4_bwd_part2 (same B, L, D) are added
+int asrx_msheath_ctrl_lens_bwd4(const float* part, const int32_t* lens, int64_t L, const float* g_mwo,
+                                const float* mem_v, const float* mem_w, int64_t ld_mem_w, const float* mem,
+                                const float* jump_s, const void* rec, int64_t layer_i, int64_t layers, int64_t B,
+                                int64_t D, float* g_policy, int acc_policy, float* g_mem_w, float* g_mem,
+                                float* g_jump_s, int* has_orig, const float* mg_w, float* g_mg_w, float* g_mg_b,
+                                hipStream_t stream) {
+  ASRX_REQUIRE(D % 4 == 0, "asrx_msheath_ctrl_bwd4: D % 4 != 0");
+  if (B == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_msheath_ctrl_lens_bwd4: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_msheath_ctrl_lens_bwd4");
+  const int64_t nlc = (L + JUMP_CHUNK - 1) / JUMP_CHUNK, ncc = (D / 4 + 31) / 32;
+  const float2* part_ab = reinterpret_cast<const float2*>(part);
+  const float* part_g = part + 2 * B * nlc * ncc;
+  msheath_ctrl_bwd_kernel<true><<<(unsigned)B, 256, 0, stream>>>(nullptr, nullptr, nullptr, g_mwo, mem_v, mem_w, mem,
+                                                                 jump_s, (const CtrlRec*)rec, (int)layer_i, (int)layers,
+                                                                 (int)D, g_policy, nullptr, g_mem_w, g_mem, g_jump_s,
+                                                                 ld_mem_w, has_orig, acc_policy, mg_w, g_mg_w, g_mg_b,
+                                                                 part_ab, part_g, (int)nlc, (int)ncc, lens, (int)L);
+  ASRX_LAUNCHED("asrx_msheath_ctrl_lens_bwd4");
+}
+
+// asrx_axpy_row2_colsum with lengths: chunk sums over live rows (a chunk with none stores a zero partial); pad rows
+// of out, when given, are stored as zeros for a sample at the layer
+int asrx_axpy_row2_lens_colsum(const float* x, const float* s1, const float* s2, const float* y, float* out,
+                               float* part, const int32_t* lens, int64_t B, int64_t L, int64_t d, const float* next_i,
+                               int64_t layer, hipStream_t stream) {
+  ASRX_REQUIRE(d % 4 == 0 && d <= 1024, "asrx_axpy_row2_colsum: d %% 4 == 0 and d <= 1024 required");
+  ASRX_REQUIRE(s2 != nullptr, "asrx_axpy_row2_colsum: s2 required");
+  if (B * L == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_axpy_row2_lens_colsum: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_axpy_row2_lens_colsum");
+  const int d4 = (int)(d / 4);
+  dim3 grid((unsigned)B, (unsigned)asrx_mem_chunks(L));
+  axpy_row2_colsum_kernel<true><<<grid, 256, 0, stream>>>((const float4*)x, s1, s2, (const float4*)y, (float4*)out,
+                                                          (float4*)part, L, d4, next_i, (int)layer, lens);
+  ASRX_LAUNCHED("asrx_axpy_row2_lens_colsum");
+}
+
+// asrx_jump_axpy_inplace with lengths: pad rows are stored as zeros when xout != xin and left alone in place
+int asrx_jump_lens_axpy_inplace(const float* xin, float* xout, const float* s1, const float* s2, const float* y,
+                                const float* orig, const float* act, const float* alpha, const float* beta,
+                                const float* gam, const int32_t* lens, int64_t B, int64_t L, int64_t d,
+                                hipStream_t stream) {
+  ASRX_REQUIRE(d % 4 == 0, "asrx_jump_axpy_inplace: d % 4 != 0");
+  ASRX_REQUIRE(xout != orig, "asrx_jump_axpy_inplace: xout must not alias orig");
+  if (B * L == 0) return 0;
+  ASRX_REQUIRE(d / 4 <= 256, "asrx_jump_axpy_inplace: d <= 1024 required");
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_jump_lens_axpy_inplace: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_jump_lens_axpy_inplace");
+  dim3 grid((unsigned)std::min<int64_t>((L * (d / 4) + 255) / 256, 512), (unsigned)B);
+  jump_axpy_inplace_kernel<true><<<grid, 256, 0, stream>>>((const float4*)xin, (float4*)xout, s1, s2, (const float4*)y,
+                                                           (const float4*)orig, act, alpha, beta, (const float4*)gam,
+                                                           L, (int)(d / 4), lens);
+  ASRX_LAUNCHED("asrx_jump_lens_axpy_inplace");
+}
+
+// asrx_jump_select4 with lengths: out's pad rows are stored as zeros, for samples at the layer or not
+int asrx_jump_lens_select4(const float* xn, const float* orig, const float* xold, const float* act,
+                           const float* alpha, const float* beta, const float* gam, float* out, const int32_t* lens,
+                           int64_t B, int64_t L, int64_t d, hipStream_t stream) {
+  ASRX_REQUIRE(d % 4 == 0 && d <= 1024, "asrx_jump_select4: d % 4 != 0 or d > 1024");
+  if (B * L == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_jump_lens_select4: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_jump_lens_select4");
+  dim3 grid((unsigned)std::min<int64_t>((L * (d / 4) + 255) / 256, 512), (unsigned)B);
+  jump_select4_kernel<true><<<grid, 256, 0, stream>>>((const float4*)xn, (const float4*)orig, (const float4*)xold, act,
+                                                      alpha, beta, (const float4*)gam, (float4*)out, L, (int)(d / 4),
+                                                      lens);
+  ASRX_LAUNCHED("asrx_jump_lens_select4");
+}
+#undef ASRX_REQUIRE_LENS
 
 }  // extern "C"

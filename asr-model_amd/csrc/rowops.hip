@@ -3,6 +3,7 @@
 // op(s) it replaces.
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 #include <mutex>
 #include <map>
 #include <unordered_map>
@@ -634,6 +635,19 @@ __global__ __launch_bounds__(64 * RW) void vgate_weights_kernel(const float* __r
   }
 }
 
+// Per-sample lengths (the LENS instantiations of the MSheath and encoder row-crossing kernels below): sample b's live
+// row count T_b of the (B,) int32 device table, clamped to the launch extent T so that a bad table cannot
+// address past it.  T keeps the grid and the addressing; T_b takes its place as the row limit: rows at or past
+// it count as zeros on the way in (never loaded) and are stored as zeros on the way out (a select, so what
+// they held, NaN included, reaches nothing).  Live values are formed by the expressions and in the order of
+// the uniform instantiation run on x[b, :T_b] alone.
+__device__ __forceinline__ int seq_len(const int32_t* __restrict__ lens, int64_t b, int T) {
+  return min(max(lens[b], 0), T);
+}
+// 1 / T_b as the uniform kernels' callers pass 1.0 / L (float(1.0 / L) == 1.0f / float(L) for every L < 2^24,
+// tests/test_msheath_lens_ref.py); 0 for an empty sample, whose means are then 0
+__device__ __forceinline__ float seq_rcp(int Tb) { return Tb > 0 ? 1.0f / (float)Tb : 0.f; }
+
 struct MSRowFwd {
   const float *x, *lnw, *lnb, *gw, *gb;                   // layer input, ln, gate Linear(D, 1)
   const float *SH, *mval, *w2, *b2, *cw, *cb, *tx;         // v_gate
@@ -657,11 +671,19 @@ struct MSRowFwd {
   // column sums and the jump skip such samples)
   int nofill;
 };
+// The LENS instantiations' argument (asrx_msheath_row_lens_fwd2 / _fwd3; the uniform ones keep MSRowFwd and with it
+// their kernarg layout): + the (B,) int32 row counts.  A row at or past its sample's T_b is treated as a row of a
+// sample not at this layer (its values are not used and zeros are stored; as for such a sample, the prefetch of a
+// row that is not live re-reads row 0 of x and SH instead, so with T_0 = 0 one pad row is loaded and its value
+// discarded), and xnew gets zeros there.
+struct MSRowFwdL : MSRowFwd {
+  const int32_t* lens;
+};
 
 // Per row: px = LayerNorm(x); nx = |x|; g = sigmoid(px . gw + gb); v_gate from SH and nx (as
 // vgate_fwd_kernel): ion = STE(cw0 softmax(S / (nx sqrt D)) . mval + cw1 (silu(h) . w2 + b2) + cb > tx).
-template <int E>
-__global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
+template <int E, bool LENS = false>
+__global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(std::conditional_t<LENS, MSRowFwdL, MSRowFwd> p) {
   constexpr int D = 64 * E;
   const int lane = threadIdx.x & 63;
   float wv[E], bv[E], gwv[E];
@@ -676,13 +698,27 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
   // order) would drain the prefetch queue.  32-bit sample index (rows < 2^31): a 64-bit division by the
   // runtime L cost ~3x the instructions.
   extern __shared__ float ni_s[];
-  if (p.next_i) {
+  if constexpr (LENS) {
+    // one int per sample in the same place (its bits in the float array): T_b of a sample at this layer, -1 of one
+    // that is not; a row is live when its index within the sample is below it
+    const int nb = (int)((p.rows + p.L - 1) / p.L);
+    for (int b = threadIdx.x; b < nb; b += 64 * RW) {
+      const bool at = !p.next_i || p.next_i[b] == (float)p.layer;
+      ni_s[b] = __int_as_float(at ? seq_len(p.lens, b, (int)p.L) : -1);
+    }
+    __syncthreads();
+  } else if (p.next_i) {
     const int nb = (int)((p.rows + p.L - 1) / p.L);
     for (int b = threadIdx.x; b < nb; b += 64 * RW) ni_s[b] = p.next_i[b];
     __syncthreads();
   }
   auto at_layer = [&](int64_t rr) __attribute__((always_inline)) -> bool {
-    return !p.next_i || ni_s[(unsigned)rr / (unsigned)p.L] == (float)p.layer;
+    if constexpr (LENS) {
+      const unsigned b = (unsigned)rr / (unsigned)p.L;
+      return (int)((unsigned)rr - b * (unsigned)p.L) < __float_as_int(ni_s[b]);
+    } else {
+      return !p.next_i || ni_s[(unsigned)rr / (unsigned)p.L] == (float)p.layer;
+    }
   };
   constexpr int HQ = (E + 1) / 2;  // h values per lane (Dh = D / 2 <= 64 HQ)
   float w2v[HQ];
@@ -710,6 +746,9 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
       for (int e = 0; e < E; ++e) z[e] = 0.f;
       if (p.pxb) st_lane<E>(p.pxb + r * D, lane, z);
       else if (p.px) st_lane<E>(p.px + r * D, lane, z);
+      if constexpr (LENS) {  // a pad row of a sample at the layer: x_new is stored there (the jump does not read it)
+        if (p.xnew && __float_as_int(ni_s[(unsigned)r / (unsigned)p.L]) >= 0) st_lane<E>(p.xnew + r * D, lane, z);
+      }
       if (lane == 0) {
         p.mean[r] = 0.f;
         p.rstd[r] = 0.f;
@@ -789,7 +828,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
     // rows w, w + RW, ... in order with the next row's loads in flight, and the RW waves' column sums are added
     // in wave order through LDS (deterministic)
     // RW x D floats after the next_i copy, 16-byte aligned (the float2 lane accesses need 8)
-    float* red = ni_s + (p.next_i ? (((p.rows + p.L - 1) / p.L + 3) & ~(int64_t)3) : 0);
+    float* red = ni_s + ((LENS || p.next_i) ? (((p.rows + p.L - 1) / p.L + 3) & ~(int64_t)3) : 0);
     const int w = threadIdx.x >> 6;
     const int64_t nb = (p.rows + p.L - 1) / p.L, nc = (int64_t)nb * p.nchunk;
     for (int64_t cid = blockIdx.x; cid < nc; cid += gridDim.x) {
@@ -797,19 +836,27 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_fwd_kernel(MSRowFwd p) {
       const int64_t r0 = b * p.L + c * 64, r1 = min(min(r0 + 64, (b + 1) * p.L), p.rows);
 #pragma unroll
       for (int e = 0; e < E; ++e) csum[e] = 0.f;
-      const bool act = r0 < r1 && at_layer(r0);  // workgroup-uniform
+      // LENS: the chunk's live rows end at rl (the sample's T_b); they are taken exactly as the uniform kernel
+      // takes the chunk of a T_b-row sample, and the chunk's pad rows are zeroed in a loop of their own below
+      int64_t rl = r1;
+      if constexpr (LENS) rl = min(r1, b * p.L + max(__float_as_int(ni_s[b]), 0));
+      const bool act = r0 < rl && at_layer(r0);  // workgroup-uniform
       if (act) {
         float xa[E], sa, ha[HQ];
         fetch(r0 + w, xa, sa, ha);
-        for (int64_t r = r0 + w; r < r1; r += RW) {
+        for (int64_t r = r0 + w; r < rl; r += RW) {
           float xv[E], hv[HQ];
 #pragma unroll
           for (int e = 0; e < E; ++e) xv[e] = xa[e];
 #pragma unroll
           for (int i = 0; i < HQ; ++i) hv[i] = ha[i];
           const float sv = sa;
-          fetch(r + RW < r1 ? r + RW : r0, xa, sa, ha);
+          fetch(r + RW < rl ? r + RW : r0, xa, sa, ha);
           row_body(r, xv, sv, hv);
+        }
+        if constexpr (LENS) {
+          float xv[E], hv[HQ];
+          for (int64_t r = rl + w; r < r1; r += RW) row_body(r, xv, 0.f, hv);  // pad rows: zeros
         }
       } else {
         float xv[E], hv[HQ];
@@ -882,6 +929,13 @@ struct MSRowBwd {
   const float *gj = nullptr, *alpha = nullptr, *gm = nullptr, *ion = nullptr;
   float invL = 0.f;
 };
+// The LENS instantiations' argument (asrx_msheath_row_lens_bwd2; the uniform ones keep MSRowBwd and with it their
+// kernarg layout): + the (B,) int32 row counts.  A row at or past its sample's T_b is treated as a row of a sample
+// not at this layer; mode 2 takes 1 / T_b for invL and, being dx's first writer for a sample at the layer, stores
+// zeros in that sample's pad rows of dx.
+struct MSRowBwdL : MSRowBwd {
+  const int32_t* lens;
+};
 
 // Per row, the backward of msheath_row_fwd: v_gate (dSH row with stride ldsh: dS already divided by
 // nx sqrt D, dh = dm2 w2 silu'(h)), the gate (dz = dg g (1 - g) onto px), the LayerNorm with the gate
@@ -892,8 +946,8 @@ struct MSRowBwd {
 // alpha, gm, invL with axpy_row2_bwd_acc's roundings, dx is only written, and the x_new backward of a layer whose
 // update is px is done here: t = g' . px, dion = g t, dg = ion t, dpx = (g ion) g'.  (There is no mode 1: forming
 // the base here while keeping the x_new backward kernel measured no gain)
-template <int E, int MODE = 0>
-__global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
+template <int E, int MODE = 0, bool LENS = false>
+__global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(std::conditional_t<LENS, MSRowBwdL, MSRowBwd> p) {
   constexpr int D = 64 * E;
   extern __shared__ float part[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -918,10 +972,19 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
   struct Pre {
     float x[E], gp[E], dx[E], gm[E], h[HQ];  // MODE 2: dx holds gj's row; a field a mode never loads is dropped
                                              // by the compiler (mode 0's register count is the parent's)
-    float s, gi, nx, g, dg, mu, rs, kv, m2, al, ion;
+    float s, gi, nx, g, dg, mu, rs, kv, m2, al, ion, il;
   };
   const int ni_off = RW * (3 * D + PN);  // next_i copy (one float per sample) after the partials
-  if (p.next_i) {
+  const int nb_s = (int)((p.rows + p.L - 1) / p.L);
+  if constexpr (LENS) {
+    // in its place one int per sample (its bits): T_b of a sample at this layer, -1 of one that is not; then 1 / T_b
+    for (int b = threadIdx.x; b < nb_s; b += 64 * RW) {
+      const bool at = !p.next_i || p.next_i[b] == (float)p.layer;
+      const int Tb = seq_len(p.lens, b, (int)p.L);
+      part[ni_off + b] = __int_as_float(at ? Tb : -1);
+      part[ni_off + nb_s + b] = seq_rcp(Tb);
+    }
+  } else if (p.next_i) {
     const int nb = (int)((p.rows + p.L - 1) / p.L);
     for (int b = threadIdx.x; b < nb; b += 64 * RW) part[ni_off + b] = p.next_i[b];
   }
@@ -930,7 +993,12 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
   // (indexed off the __shared__ array itself: through a captured float* the accesses lost their
   // address space and became global loads)
   auto at_layer = [&](int64_t rr) __attribute__((always_inline)) -> bool {
-    return !p.next_i || part[ni_off + (int)((unsigned)rr / (unsigned)p.L)] == (float)p.layer;
+    if constexpr (LENS) {
+      const unsigned b = (unsigned)rr / (unsigned)p.L;
+      return (int)((unsigned)rr - b * (unsigned)p.L) < __float_as_int(part[ni_off + (int)b]);
+    } else {
+      return !p.next_i || part[ni_off + (int)((unsigned)rr / (unsigned)p.L)] == (float)p.layer;
+    }
   };
   float w2v[HQ];
 #pragma unroll
@@ -950,6 +1018,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
       ld_lane<E>(p.gj + rc * D, lane, q.dx);
       ld_lane<E>(p.gm + bc * D, lane, q.gm);
       q.al = p.alpha[bc];
+      if constexpr (LENS) q.il = part[ni_off + nb_s + (int)bc];
     }
     if constexpr (MODE == 2) {
       q.ion = p.ion[rc];
@@ -975,6 +1044,14 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
     if (!at_layer(r)) {
       float* dz = p.dSH + r * p.ldsh;  // zero rows: the weight-gradient GEMMs sum over every row
       for (int j = lane; j < M + Dh; j += 64) dz[j] = 0.f;
+      if constexpr (LENS && MODE == 2) {  // a pad row of a sample at the layer: this pass is dx's first writer
+        if (__float_as_int(part[ni_off + (int)((unsigned)r / (unsigned)p.L)]) >= 0) {
+          float z[E];
+#pragma unroll
+          for (int e = 0; e < E; ++e) z[e] = 0.f;
+          st_lane<E>(p.dx + r * D, lane, z);
+        }
+      }
       return;
     }
     // dx's base: MODE 0 what dx holds; else g' = alpha gj + gm invL, each product rounded on its own as
@@ -988,7 +1065,7 @@ __global__ __launch_bounds__(64 * RW) void msheath_row_bwd_kernel(MSRowBwd p) {
         base[e] = c.dx[e];
       } else {
         const float dxn = c.al * c.dx[e];
-        const float gmL = c.gm[e] * p.invL;
+        const float gmL = c.gm[e] * (LENS ? c.il : p.invL);
         base[e] = dxn + gmL;
       }
       if constexpr (MODE != 2) gpx[e] = c.gp[e];
@@ -1183,9 +1260,25 @@ __global__ void axpy_row_kernel(const float* __restrict__ x, const float* __rest
 
 // float4 form (d % 4 == 0, aligned, rows * d / 4 < 2^31): two vectors per thread and trip, loads first,
 // 32-bit row index; the same x + s * y per element (bit-identical; this unit builds without contractions)
+// LENS (asrx_axpy_lens_row, L rows per sample): a row at or past its sample's T_b stores zeros and loads nothing.
+template <bool LENS = false>
 __global__ void axpy_row4_kernel(const float4* __restrict__ x, const float* __restrict__ s,
-                                 const float4* __restrict__ y, float4* __restrict__ out, uint32_t n4, uint32_t d4) {
+                                 const float4* __restrict__ y, float4* __restrict__ out, uint32_t n4, uint32_t d4,
+                                 uint32_t L = 0, const int32_t* __restrict__ lens = nullptr) {
   const uint32_t st = gridDim.x * blockDim.x;
+  if constexpr (LENS) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += st) {
+      const uint32_t r = i / d4, b = r / L;
+      float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+      if ((int)(r - b * L) < seq_len(lens, b, (int)L)) {
+        const float4 xv = x[i], yv = y[i];
+        const float sc = s ? s[r] : 1.f;
+        o = make_float4(xv.x + sc * yv.x, xv.y + sc * yv.y, xv.z + sc * yv.z, xv.w + sc * yv.w);
+      }
+      out[i] = o;
+    }
+    return;
+  }
   auto one = [&](uint32_t i, float4 xv, float4 yv) __attribute__((always_inline)) {
     const float sc = s ? s[i / d4] : 1.f;
     out[i] = make_float4(xv.x + sc * yv.x, xv.y + sc * yv.y, xv.z + sc * yv.z, xv.w + sc * yv.w);
@@ -1201,12 +1294,27 @@ __global__ void axpy_row4_kernel(const float4* __restrict__ x, const float* __re
 
 // ds[r] = sum_j g[r,j] * y[r,j] ;  dy = s[r] * g  (dy may alias nothing)
 // (dxc, when non-null, receives a copy of g: x's pass-through gradient as a buffer the caller owns)
+// LENS (asrx_axpy_lens_row_bwd2, L rows per sample): a row at or past its sample's T_b reads nothing and gets
+// dy = 0, ds = 0, dxc = 0.
+template <bool LENS = false>
 __global__ __launch_bounds__(64 * RW) void axpy_row_bwd_kernel(const float* __restrict__ g, const float* __restrict__ s,
                                                                const float* __restrict__ y, float* __restrict__ dy,
                                                                float* __restrict__ ds, int64_t rows, int d,
-                                                               float* __restrict__ dxc) {
+                                                               float* __restrict__ dxc, int64_t L = 0,
+                                                               const int32_t* __restrict__ lens = nullptr) {
   const int lane = threadIdx.x & 63;
   for (int64_t r = row_begin(); r < rows; r += row_step()) {
+    if constexpr (LENS) {
+      const int64_t b = r / L;
+      if ((int)(r - b * L) >= seq_len(lens, b, (int)L)) {
+        for (int j = lane; j < d; j += 64) {
+          dy[r * d + j] = 0.f;
+          if (dxc) dxc[r * d + j] = 0.f;
+        }
+        if (lane == 0) ds[r] = 0.f;
+        continue;
+      }
+    }
     const float sc = s[r];
     float acc = 0.f;
     for (int j = lane; j < d; j += 64) {
@@ -1309,13 +1417,20 @@ __global__ __launch_bounds__(256) void seg_colsum_kernel(const float* __restrict
 
 // Deterministic form (forward values feeding hard decisions, model.py:432 MPNet pooling): chunk sums
 // to part[b][chunk][:] with no atomics, then seg_reduce adds the chunks in order.
+// LENS (asrx_seg_colsum_lens_det): the rows stop at the sample's T_b, and seg_reduce adds its first
+// ceil(T_b / chunk) chunks only (a prefix of the slots L lays out; a dead chunk's zero is not added, -0 + 0 is
+// not -0) times 1 / T_b: sample b's means come out as those of x[b, :T_b] alone.
+template <bool LENS = false>
 __global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restrict__ x, float* __restrict__ part,
-                                                          int64_t L, int d, int64_t chunk) {
+                                                          int64_t L, int d, int64_t chunk,
+                                                          const int32_t* __restrict__ lens = nullptr) {
   __shared__ float red[4][64];
   const int b = blockIdx.y;
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const int p4 = threadIdx.x >> 6;
-  const int64_t l0 = (int64_t)blockIdx.z * chunk, l1 = min(L, l0 + chunk);
+  int64_t Lb = L;
+  if constexpr (LENS) Lb = seq_len(lens, b, (int)L);
+  const int64_t l0 = (int64_t)blockIdx.z * chunk, l1 = min(Lb, l0 + chunk);
   float s = 0.f;
   if (c < d)
     for (int64_t l = l0 + p4; l < l1; l += 4) s += x[((int64_t)b * L + l) * d + c];
@@ -1327,19 +1442,26 @@ __global__ __launch_bounds__(256) void seg_partial_kernel(const float* __restric
   }
 }
 
+template <bool LENS = false>
 __global__ void seg_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int B, int nchunk, int d,
-                                  float scale) {
+                                  float scale, const int32_t* __restrict__ lens = nullptr, int L = 0, int chunk = 1) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * d) return;
   const int64_t b = i / d, c = i % d;
+  int nc = nchunk;  // the chunks added; nchunk stays the slot stride
+  if constexpr (LENS) {
+    const int Tb = seq_len(lens, b, L);
+    nc = (Tb + chunk - 1) / chunk;
+    scale = seq_rcp(Tb);
+  }
   float t = 0.f;
-  for (int k = 0; k < nchunk; k += 16) {  // in chunk order, 16 loads in flight (the last group's clamped)
+  for (int k = 0; k < nc; k += 16) {  // in chunk order, 16 loads in flight (the last group's clamped)
     float v[16];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = part[(b * nchunk + min(k + j, nchunk - 1)) * d + c];
+    for (int j = 0; j < 16; ++j) v[j] = part[(b * nchunk + min(k + j, nc - 1)) * d + c];
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      if (k + j < nchunk) t += v[j];
+      if (k + j < nc) t += v[j];
   }
   out[i] = t * scale;
 }
@@ -1453,16 +1575,6 @@ __global__ void lincomb4_kernel(const float4* __restrict__ x, const float4* __re
   }
   if (i < n4) out[i] = one(x[i], y ? y[i] : zero, z ? z[i] : zero);
 }
-// Per-sample lengths (the LENS instantiations of the encoder's row-crossing kernels below): sample b's live
-// row count T_b of the (B,) int32 device table, clamped to the launch extent T so that a bad table cannot
-// address past it.  T keeps the grid and the addressing; T_b takes its place as the row limit: rows at or past
-// it count as zeros on the way in (never loaded) and are stored as zeros on the way out (a select, so what
-// they held, NaN included, reaches nothing).  Live values are formed by the expressions and in the order of
-// the uniform instantiation run on x[b, :T_b] alone.
-__device__ __forceinline__ int seq_len(const int32_t* __restrict__ lens, int64_t b, int T) {
-  return min(max(lens[b], 0), T);
-}
-
 template <bool LENS = false>
 __global__ void act_fwd4_kernel(const float4* __restrict__ x, float4* __restrict__ y, uint32_t n4, int act,
                                 uint32_t C4, uint32_t T, const int32_t* __restrict__ lens) {
@@ -3028,6 +3140,131 @@ int asrx_msheath_row_bwd2(int mode, const float* gj, const float* alpha, const f
   MS_DISPATCH_MODE(2, row_grid(rows, 1024), shm, p);
   ASRX_LAUNCHED("asrx_msheath_row_bwd2");
 }
+
+// ---- MSheath with per-sample lengths: the LENS instantiations of the row kernels.  `lens` is a device table of B
+// int32 (asrx_act_lens_fwd's), T_b = lens[b] clamped to [0, L]; a row at or past T_b is treated exactly like a row
+// of a sample that is not at the layer.  Each entry point is its uniform twin with `lens` ahead of the sizes, gives
+// the twin's refusals in the twin's words, then refuses a null and a misaligned table.  nofill is passed as 0: these
+// never read the process-global flag of the no-grad composite.
+#define ASRX_REQUIRE_LENS(name)                                                                 \
+  ASRX_REQUIRE(lens != nullptr, name ": per-sample lengths: null table");                       \
+  ASRX_REQUIRE(((uintptr_t)lens & 3) == 0, name ": per-sample lengths: table must be 4-byte aligned")
+#define MS_DISPATCH_LENS(KER, GRID, SHM, P)                                        \
+  switch (d) {                                                                     \
+    case 128: KER<2, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;              \
+    case 256: KER<4, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;              \
+    case 384: KER<6, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;              \
+    case 512: KER<8, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;              \
+    case 768: KER<12, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;             \
+    case 1024: KER<16, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    default: ASRX_REQUIRE(false, #KER ": d=%ld unsupported", (long)d);             \
+  }
+#define MS_DISPATCH_MODE_LENS(MODE, GRID, SHM, P)                                                         \
+  switch (d) {                                                                                            \
+    case 128: msheath_row_bwd_kernel<2, MODE, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 256: msheath_row_bwd_kernel<4, MODE, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 384: msheath_row_bwd_kernel<6, MODE, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 512: msheath_row_bwd_kernel<8, MODE, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;            \
+    case 768: msheath_row_bwd_kernel<12, MODE, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;           \
+    case 1024: msheath_row_bwd_kernel<16, MODE, true><<<GRID, 64 * RW, SHM, stream>>>(P); break;          \
+    default: ASRX_REQUIRE(false, "asrx_msheath_row_bwd2: d=%ld unsupported", (long)d);                    \
+  }
+
+// asrx_msheath_row_fwd2 with lengths (rows = B L required: the table has one entry per sample)
+int asrx_msheath_row_lens_fwd2(const float* x, const float* lnw, const float* lnb, const float* gw, const float* gb,
+                               const float* SH, int64_t ldsh, const float* mval, const float* w2, const float* b2,
+                               const float* cw, const float* cb, const float* tx, void* px, int px_bf16, float* mean,
+                               float* rstd, float* nx, float* g, float* ion, float* kv, float* m2,
+                               const int32_t* lens, int64_t rows, int64_t d, int64_t M, int64_t Dh, float eps,
+                               float inv_sqrt_d, const float* next_i, int64_t layer, int64_t L, hipStream_t stream) {
+  ASRX_REQUIRE(M <= 64 && ldsh >= M + Dh, "asrx_msheath_row_fwd: M <= 64 and ldsh >= M + Dh required");
+  ASRX_REQUIRE(Dh <= 64 * ((d / 64 + 1) / 2), "asrx_msheath_row_fwd: v_gate hidden size Dh <= d / 2 required");
+  ASRX_REQUIRE(ms_aligned({x, lnw, lnb, gw, (const float*)px}), "asrx_msheath_row_fwd: 8-byte aligned rows required");
+  ASRX_REQUIRE(!next_i || L > 0, "asrx_msheath_row_fwd: L > 0 required with next_i");
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(L > 0 && rows % L == 0 && rows < (1LL << 31), "asrx_msheath_row_lens_fwd2: rows = B L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_msheath_row_lens_fwd2");
+  MSRowFwdL p{{x, lnw, lnb, gw, gb, SH, mval, w2, b2, cw, cb, tx, px_bf16 ? nullptr : (float*)px, mean, rstd, nx, g,
+               ion, kv, m2, rows, ldsh, (int)M, (int)Dh, eps, inv_sqrt_d, next_i, (int)layer, L,
+               px_bf16 ? (unsigned short*)px : nullptr, nullptr, nullptr, 0, 0},
+              lens};
+  const size_t shm = (size_t)(rows / L) * sizeof(float);  // the per-sample row limits
+  ASRX_REQUIRE(shm <= 48 * 1024, "msheath_row_fwd: %ld samples exceed the next_i LDS copy", (long)(shm / 4));
+  MS_DISPATCH_LENS(msheath_row_fwd_kernel, row_grid(rows), shm, p);
+  ASRX_LAUNCHED("asrx_msheath_row_lens_fwd2");
+}
+
+// asrx_msheath_row_fwd3 with lengths: a chunk's column sums take its live rows only (a chunk with none stores a zero
+// partial), and xnew gets zeros in the pad rows of a sample at the layer
+int asrx_msheath_row_lens_fwd3(const float* x, const float* lnw, const float* lnb, const float* gw, const float* gb,
+                               const float* SH, int64_t ldsh, const float* mval, const float* w2, const float* b2,
+                               const float* cw, const float* cb, const float* tx, float* px, float* mean, float* rstd,
+                               float* nx, float* g, float* ion, float* kv, float* m2, float* xnew, float* part,
+                               const int32_t* lens, int64_t rows, int64_t d, int64_t M, int64_t Dh, float eps,
+                               float inv_sqrt_d, const float* next_i, int64_t layer, int64_t L, hipStream_t stream) {
+  ASRX_REQUIRE(M <= 64 && ldsh >= M + Dh, "asrx_msheath_row_fwd3: M <= 64 and ldsh >= M + Dh required");
+  ASRX_REQUIRE(Dh <= 64 * ((d / 64 + 1) / 2), "asrx_msheath_row_fwd3: v_gate hidden size Dh <= d / 2 required");
+  ASRX_REQUIRE(ms_aligned({x, lnw, lnb, gw, (const float*)px, (const float*)xnew, (const float*)part}),
+               "asrx_msheath_row_fwd3: 8-byte aligned rows required");
+  ASRX_REQUIRE(part && L > 0 && rows % L == 0, "asrx_msheath_row_fwd3: part and rows = B L required");
+  ASRX_REQUIRE(px || xnew, "asrx_msheath_row_fwd3: px or xnew required");
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(rows < (1LL << 31), "asrx_msheath_row_lens_fwd3: rows = B L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_msheath_row_lens_fwd3");
+  MSRowFwdL p{{x, lnw, lnb, gw, gb, SH, mval, w2, b2, cw, cb, tx, px, mean, rstd, nx, g, ion, kv, m2, rows, ldsh,
+               (int)M, (int)Dh, eps, inv_sqrt_d, next_i, (int)layer, L, nullptr, part, xnew, (int)((L + 63) / 64), 0},
+              lens};
+  // the per-sample row limits, then the RW waves' column sums of a chunk
+  const size_t shm = (size_t)((rows / L + 3) & ~(int64_t)3) * sizeof(float) + (size_t)RW * d * sizeof(float);
+  ASRX_REQUIRE(shm <= 48 * 1024, "msheath_row_fwd3: %ld samples exceed the next_i LDS copy", (long)(rows / L));
+  const int64_t chunks = (rows / L) * p.nchunk;
+  MS_DISPATCH_LENS(msheath_row_fwd_kernel, (unsigned)std::min<int64_t>(chunks, 65535), shm, p);
+  ASRX_LAUNCHED("asrx_msheath_row_lens_fwd3");
+}
+
+// asrx_msheath_row_bwd2 with lengths, modes 0 and 2.  invL is computed per sample (1 / T_b); pad rows get dSH = 0,
+// add nothing to a parameter gradient and, in mode 2 for a sample at the layer, dx = 0.
+int asrx_msheath_row_lens_bwd2(int mode, const float* gj, const float* alpha, const float* gm, const float* ion,
+                               const float* dpx, const float* x, const float* lnw, const float* lnb,
+                               const float* mean, const float* rstd, const float* dg, const float* g, const float* gw,
+                               const float* dion, const float* SH, int64_t ldsh, const float* nx, const float* mval,
+                               const float* w2, const float* cw, const float* kv, const float* m2, float* dx,
+                               float* dlnw, float* dlnb, float* dgw, float* dgb, float* dSH, float* dmval, float* dw2,
+                               float* db2, float* dcw, float* dcb, float* db1, const int32_t* lens, int64_t rows,
+                               int64_t d, int64_t M, int64_t Dh, float inv_sqrt_d, const float* next_i, int64_t layer,
+                               int64_t L, hipStream_t stream) {
+  ASRX_REQUIRE(mode == 0 || mode == 2, "asrx_msheath_row_bwd2: mode 0 or 2");
+  if (mode == 0) {
+    ASRX_REQUIRE(M <= 64 && ldsh >= M + Dh, "asrx_msheath_row_bwd: M <= 64 and ldsh >= M + Dh required");
+    ASRX_REQUIRE(Dh <= 64 * ((d / 64 + 1) / 2), "asrx_msheath_row_bwd: v_gate hidden size Dh <= d / 2 required");
+    ASRX_REQUIRE(ms_aligned({dpx, x, lnw, lnb, gw, dx}), "asrx_msheath_row_bwd: 8-byte aligned rows required");
+    ASRX_REQUIRE(!next_i || L > 0, "asrx_msheath_row_bwd: L > 0 required with next_i");
+  } else {
+    ASRX_REQUIRE(M <= 64 && ldsh >= M + Dh, "asrx_msheath_row_bwd2: M <= 64 and ldsh >= M + Dh required");
+    ASRX_REQUIRE(Dh <= 64 * ((d / 64 + 1) / 2), "asrx_msheath_row_bwd2: v_gate hidden size Dh <= d / 2 required");
+    ASRX_REQUIRE(gj && alpha && gm && L > 0 && rows % L == 0, "asrx_msheath_row_bwd2: gj, alpha, gm and rows = B L required");
+    ASRX_REQUIRE(ion, "asrx_msheath_row_bwd2: mode 2 reads ion");
+    ASRX_REQUIRE(ms_aligned({gj, gm, dpx, x, lnw, lnb, gw, dx}), "asrx_msheath_row_bwd2: 8-byte aligned rows required");
+  }
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(L > 0 && rows % L == 0 && rows < (1LL << 31), "asrx_msheath_row_lens_bwd2: rows = B L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_msheath_row_lens_bwd2");
+  MSRowBwdL p{{dpx, x, lnw, lnb, mean, rstd, dg, g, gw, dion, SH, nx, mval, w2, cw, kv, m2, dx, dlnw, dlnb, dgw, dgb,
+               dSH, dmval, dw2, db2, dcw, dcb, db1, rows, ldsh, (int)M, (int)Dh, inv_sqrt_d, next_i, (int)layer, L,
+               gj, alpha, gm, ion, 0.f},
+              lens};
+  const size_t nb = (size_t)(rows / L);  // + the per-sample row limits and reciprocals
+  const size_t shm = ((size_t)RW * (3 * d + M + 2 * Dh + 5) + 2 * nb) * sizeof(float);
+  ASRX_REQUIRE(shm <= 160 * 1024, "msheath_row_bwd2: %ld samples exceed the LDS budget", (long)nb);
+  if (mode == 0) {
+    MS_DISPATCH_MODE_LENS(0, row_grid(rows, 1024), shm, p);
+  } else {
+    MS_DISPATCH_MODE_LENS(2, row_grid(rows, 1024), shm, p);
+  }
+  ASRX_LAUNCHED("asrx_msheath_row_lens_bwd2");
+}
+#undef MS_DISPATCH_MODE_LENS
+#undef MS_DISPATCH_LENS
 #undef MS_DISPATCH_MODE
 #undef MS_DISPATCH
 
@@ -3058,7 +3295,7 @@ int asrx_axpy_row(const float* x, const float* s, const float* y, float* out, in
   if (d % 4 == 0 && rows * d / 4 < (1LL << 31) &&
       ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15) == 0)) {
     const int64_t n4 = rows * d / 4;
-    axpy_row4_kernel<<<ew_grid((n4 + 1) / 2, 8192), 256, 0, stream>>>((const float4*)x, s, (const float4*)y,
+    axpy_row4_kernel<false><<<ew_grid((n4 + 1) / 2, 8192), 256, 0, stream>>>((const float4*)x, s, (const float4*)y,
                                                                       (float4*)out, (uint32_t)n4, (uint32_t)(d / 4));
   } else {
     LAUNCH_EW(axpy_row_kernel, rows * d, x, s, y, out, rows, (int)d);
@@ -3069,15 +3306,40 @@ int asrx_axpy_row(const float* x, const float* s, const float* y, float* out, in
 int asrx_axpy_row_bwd(const float* g, const float* s, const float* y, float* dy, float* ds, int64_t rows, int64_t d,
                       hipStream_t stream) {
   if (rows == 0) return 0;
-  LAUNCH_ROWS(axpy_row_bwd_kernel, rows, 0, g, s, y, dy, ds, rows, (int)d, (float*)nullptr);
+  LAUNCH_ROWS(axpy_row_bwd_kernel<false>, rows, 0, g, s, y, dy, ds, rows, (int)d, (float*)nullptr);
   ASRX_LAUNCHED("asrx_axpy_row_bwd");
 }
 
 int asrx_axpy_row_bwd2(const float* g, const float* s, const float* y, float* dy, float* ds, float* dxc, int64_t rows,
                        int64_t d, hipStream_t stream) {
   if (rows == 0) return 0;
-  LAUNCH_ROWS(axpy_row_bwd_kernel, rows, 0, g, s, y, dy, ds, rows, (int)d, dxc);
+  LAUNCH_ROWS(axpy_row_bwd_kernel<false>, rows, 0, g, s, y, dy, ds, rows, (int)d, dxc);
   ASRX_LAUNCHED("asrx_axpy_row_bwd2");
+}
+
+// asrx_axpy_row on (B, L, d) with lengths (the float4 form only): out = live ? x + s y : 0
+int asrx_axpy_lens_row(const float* x, const float* s, const float* y, float* out, const int32_t* lens, int64_t B,
+                       int64_t L, int64_t d, hipStream_t stream) {
+  if (B * L == 0) return 0;
+  ASRX_REQUIRE(d > 0 && d % 4 == 0 && B * L * d / 4 < (1LL << 31) &&
+                   ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15) == 0),
+               "asrx_axpy_lens_row: needs d %% 4 == 0, 16-byte aligned tensors and B*L*d/4 < 2^31");
+  ASRX_REQUIRE_LENS("asrx_axpy_lens_row");
+  const int64_t n4 = B * L * d / 4;
+  axpy_row4_kernel<true><<<ew_grid(n4, 8192), 256, 0, stream>>>((const float4*)x, s, (const float4*)y, (float4*)out,
+                                                                (uint32_t)n4, (uint32_t)(d / 4), (uint32_t)L, lens);
+  ASRX_LAUNCHED("asrx_axpy_lens_row");
+}
+
+// asrx_axpy_row_bwd2 on (B, L, d) with lengths: pad rows of g are not read; dy, ds and dxc are zero there
+int asrx_axpy_lens_row_bwd2(const float* g, const float* s, const float* y, float* dy, float* ds, float* dxc,
+                            const int32_t* lens, int64_t B, int64_t L, int64_t d, hipStream_t stream) {
+  const int64_t rows = B * L;
+  if (rows == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_axpy_lens_row_bwd2: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_axpy_lens_row_bwd2");
+  LAUNCH_ROWS(axpy_row_bwd_kernel<true>, rows, 0, g, s, y, dy, ds, rows, (int)d, dxc, L, lens);
+  ASRX_LAUNCHED("asrx_axpy_lens_row_bwd2");
 }
 
 int asrx_jump_select(const float* xn, const float* orig, const float* xold, const float* act, const float* alpha,
@@ -3114,9 +3376,26 @@ int asrx_seg_colsum_det(const float* x, float* part, float* out, int64_t B, int6
   if (B == 0) return 0;
   const int64_t chunk = 64, nchunk = (L + chunk - 1) / chunk;
   dim3 grid((unsigned)((d + 63) / 64), (unsigned)B, (unsigned)nchunk);
-  seg_partial_kernel<<<grid, 256, 0, stream>>>(x, part, L, (int)d, chunk);
-  seg_reduce_kernel<<<(unsigned)((B * d + 255) / 256), 256, 0, stream>>>(part, out, (int)B, (int)nchunk, (int)d, scale);
+  seg_partial_kernel<false><<<grid, 256, 0, stream>>>(x, part, L, (int)d, chunk);
+  seg_reduce_kernel<false><<<(unsigned)((B * d + 255) / 256), 256, 0, stream>>>(part, out, (int)B, (int)nchunk, (int)d, scale);
   ASRX_LAUNCHED("asrx_seg_colsum_det");
+}
+
+// asrx_seg_colsum_det with lengths: out (B, d) = (1 / T_b) sum over rows [0, T_b) of x[b], as the twin gives it for
+// x[b, :T_b] alone with scale 1 / T_b (the first ceil(T_b / 64) chunk sums, in order); 0 for T_b = 0
+int asrx_seg_colsum_lens_det(const float* x, float* part, float* out, const int32_t* lens, int64_t B, int64_t L,
+                             int64_t d, hipStream_t stream) {
+  if (B == 0) return 0;
+  ASRX_REQUIRE(L < (1LL << 31), "asrx_seg_colsum_lens_det: L < 2^31 required");
+  ASRX_REQUIRE_LENS("asrx_seg_colsum_lens_det");
+  const int64_t chunk = 64, nchunk = (L + chunk - 1) / chunk;
+  if (nchunk > 0) {
+    dim3 grid((unsigned)((d + 63) / 64), (unsigned)B, (unsigned)nchunk);
+    seg_partial_kernel<true><<<grid, 256, 0, stream>>>(x, part, L, (int)d, chunk, lens);
+  }
+  seg_reduce_kernel<true><<<(unsigned)((B * d + 255) / 256), 256, 0, stream>>>(part, out, (int)B, (int)nchunk, (int)d,
+                                                                              0.f, lens, (int)L, (int)chunk);
+  ASRX_LAUNCHED("asrx_seg_colsum_lens_det");
 }
 
 int asrx_colsum(const float* x, float* out, int64_t rows, int64_t d, hipStream_t stream) {
@@ -3186,9 +3465,7 @@ int asrx_act_fwd(const float* x, float* y, int64_t n, int act, hipStream_t strea
 // arguments plus `lens` (B int32 on the device) ahead of the sizes, keeps the twin's early return and refusals in
 // place and words, refuses what only the twin's non-float4 fall-back would take, then a null and a misaligned
 // table; every check answers before anything is launched.
-#define ASRX_REQUIRE_LENS(name)                                                                 \
-  ASRX_REQUIRE(lens != nullptr, name ": per-sample lengths: null table");                       \
-  ASRX_REQUIRE(((uintptr_t)lens & 3) == 0, name ": per-sample lengths: table must be 4-byte aligned")
+// (ASRX_REQUIRE_LENS: above, ahead of the MSheath row entry points)
 
 static bool lens_vec_ok(std::initializer_list<const void*> ps, int64_t B, int64_t T, int64_t C) {
   uintptr_t al = 0;

@@ -658,6 +658,98 @@ int asrx_bn_silu_lens_fwd(const float* x, const float* w, const float* b, float*
 int asrx_bn_silu_lens_bwd(const float* g, const float* x, const float* mean, const float* rstd, const float* w,
                           const float* b, float* sg_ws, float* sgx_ws, float* dx, float* dw, float* db,
                           const int32_t* lens, int64_t B, int64_t T, int64_t C, asrx_stream_t stream);
+/* ---- MSheath with per-sample lengths: in a zero-padded batch, sample b comes out as it would alone ----
+ * `lens` as above (B int32 on the device), T_b = lens[b] clamped to [0, L]; L stays the launch extent (grid,
+ * addressing, the slots of the chunk partials).  A row at or past T_b is treated exactly like a row of a sample
+ * that is not at the layer: its values are not used (the row kernels' prefetch loads row 0 of x and SH in place of a
+ * row that is not live and discards it, the other kernels do not load pad rows at all), and every tensor a GEMM, a column sum or a later layer reads holds
+ * zeros there (px, the seven row scalars, x_new, the jump output, y; dSH, dy, ds, dx and the first-written pad rows
+ * of dxn and dorig).  The means (pooled, mem, potential) are sums over rows [0, T_b) times 1 / T_b, formed on the
+ * device where the uniform twin takes 1 / L as an argument; the sums take the chunk partials that hold live rows,
+ * a prefix of the slots, in the twin's order, so live rows equal the twin's on x[b:b+1, :T_b] bit for bit.
+ * T_b = 0 (which asrx.ops.seq_lens refuses) gives zero rows, a reciprocal taken as 0 and zero means.  Each entry
+ * point is its twin with `lens` ahead of the sizes: the twin's refusals in the twin's words, the early return where
+ * the twin has it, then a null and a misaligned table are refused.  Pad rows of the forward's input must be finite
+ * (layer 0's weight gradient multiplies zero rows of dSH by them); their values reach no result. */
+/* asrx_seg_colsum_det with scale 1 / T_b: out[b] = mean over rows [0, T_b) (0 for T_b = 0) */
+int asrx_seg_colsum_lens_det(const float* x, float* part, float* out, const int32_t* lens, int64_t B, int64_t L,
+                             int64_t d, asrx_stream_t stream);
+/* asrx_msheath_row_fwd2 / _fwd3 (rows = B L required).  fwd3: a chunk with no live row stores a zero partial and
+ * xnew gets zeros in the pad rows of a sample at the layer.  Neither reads the no-grad composite's nofill flag. */
+int asrx_msheath_row_lens_fwd2(const float* x, const float* lnw, const float* lnb, const float* gw, const float* gb,
+                               const float* SH, int64_t ldsh, const float* mval, const float* w2, const float* b2,
+                               const float* cw, const float* cb, const float* tx, void* px, int px_bf16, float* mean,
+                               float* rstd, float* nx, float* g, float* ion, float* kv, float* m2,
+                               const int32_t* lens, int64_t rows, int64_t d, int64_t M, int64_t Dh, float eps,
+                               float inv_sqrt_d, const float* next_i, int64_t layer, int64_t L, asrx_stream_t stream);
+int asrx_msheath_row_lens_fwd3(const float* x, const float* lnw, const float* lnb, const float* gw, const float* gb,
+                               const float* SH, int64_t ldsh, const float* mval, const float* w2, const float* b2,
+                               const float* cw, const float* cb, const float* tx, float* px, float* mean, float* rstd,
+                               float* nx, float* g, float* ion, float* kv, float* m2, float* xnew, float* part,
+                               const int32_t* lens, int64_t rows, int64_t d, int64_t M, int64_t Dh, float eps,
+                               float inv_sqrt_d, const float* next_i, int64_t layer, int64_t L, asrx_stream_t stream);
+/* asrx_msheath_row_bwd2, modes 0 and 2, without invL (1 / T_b per sample): pad rows get dSH = 0, add nothing to a
+ * parameter gradient and, in mode 2 for a sample at the layer, dx = 0 */
+int asrx_msheath_row_lens_bwd2(int mode, const float* gj, const float* alpha, const float* gm, const float* ion,
+                               const float* dpx, const float* x, const float* lnw, const float* lnb,
+                               const float* mean, const float* rstd, const float* dg, const float* g, const float* gw,
+                               const float* dion, const float* SH, int64_t ldsh, const float* nx, const float* mval,
+                               const float* w2, const float* cw, const float* kv, const float* m2, float* dx,
+                               float* dlnw, float* dlnb, float* dgw, float* dgb, float* dSH, float* dmval, float* dw2,
+                               float* db2, float* dcw, float* dcb, float* db1, const int32_t* lens, int64_t rows,
+                               int64_t d, int64_t M, int64_t Dh, float inv_sqrt_d, const float* next_i, int64_t layer,
+                               int64_t L, asrx_stream_t stream);
+/* asrx_axpy_row on (B, L, d), the float4 form only (d % 4 == 0, 16-byte aligned), and asrx_axpy_row_bwd2 */
+int asrx_axpy_lens_row(const float* x, const float* s, const float* y, float* out, const int32_t* lens, int64_t B,
+                       int64_t L, int64_t d, asrx_stream_t stream);
+int asrx_axpy_lens_row_bwd2(const float* g, const float* s, const float* y, float* dy, float* ds, float* dxc,
+                            const int32_t* lens, int64_t B, int64_t L, int64_t d, asrx_stream_t stream);
+/* asrx_axpy_row2_colsum: chunk sums over live rows; out's pad rows are zeros for a sample at the layer */
+int asrx_axpy_row2_lens_colsum(const float* x, const float* s1, const float* s2, const float* y, float* out,
+                               float* part, const int32_t* lens, int64_t B, int64_t L, int64_t d, const float* next_i,
+                               int64_t layer, asrx_stream_t stream);
+/* asrx_msheath_ctrl_fwd3: mem over the first ceil(T_b / 64) chunk partials times 1 / T_b, potential over ion rows
+ * below T_b divided by T_b */
+int asrx_msheath_ctrl_lens_fwd3(const float* policy, const float* gpol, int64_t ld_gpol, const float* ion,
+                                const float* mg_w, const float* mg_b, float* mem_v_out, const float* mem_w,
+                                int64_t ld_mem_w, const float* mem_part, float* mem, const float* jump_s,
+                                const float* next_i, int64_t layer_i, int64_t layers, const int32_t* lens, int64_t B,
+                                int64_t L, int64_t D, float* alpha, float* beta, float* gam, float* mem_w_out,
+                                float* active, float* next_out, void* rec, asrx_stream_t stream);
+/* asrx_jump_select4 and asrx_jump_axpy_inplace: pad rows are stored as zeros (in place: left as they are) */
+int asrx_jump_lens_select4(const float* xn, const float* orig, const float* xold, const float* act,
+                           const float* alpha, const float* beta, const float* gam, float* out, const int32_t* lens,
+                           int64_t B, int64_t L, int64_t d, asrx_stream_t stream);
+int asrx_jump_lens_axpy_inplace(const float* xin, float* xout, const float* s1, const float* s2, const float* y,
+                                const float* orig, const float* act, const float* alpha, const float* beta,
+                                const float* gam, const int32_t* lens, int64_t B, int64_t L, int64_t d,
+                                asrx_stream_t stream);
+/* asrx_jump_select4_bwd_part2 (dxn may be null): pad rows of g are not read; the pad rows of dxn, of a first jump's
+ * dorig and of an inactive sample's dx are zeros.  asrx_msheath_ctrl_bwd4 then adds the first ceil(T_b / 128)
+ * L-chunks of the partials (same B, L, D). */
+int asrx_jump_lens_select4_bwd_part2(const float* g, const float* xn, const float* orig, const float* act,
+                                     const float* alpha, const float* beta, const int* has_orig, float* dxn,
+                                     float* dorig, float* dx, float* part, const int32_t* lens, int64_t B, int64_t L,
+                                     int64_t d, asrx_stream_t stream);
+int asrx_msheath_ctrl_lens_bwd4(const float* part, const int32_t* lens, int64_t L, const float* g_mwo,
+                                const float* mem_v, const float* mem_w, int64_t ld_mem_w, const float* mem,
+                                const float* jump_s, const void* rec, int64_t layer_i, int64_t layers, int64_t B,
+                                int64_t D, float* g_policy, int acc_policy, float* g_mem_w, float* g_mem,
+                                float* g_jump_s, int* has_orig, const float* mg_w, float* g_mg_w, float* g_mg_b,
+                                asrx_stream_t stream);
+/* asrx_axpy_row2_bwd_acc (alpha null) and asrx_axpy_row2_bwd_acc2 (alpha given) without invL: g' = [alpha] g + gm / T_b;
+ * a pad row gets dy = 0, ds = 0 and, for an active sample, dx = 0 */
+int asrx_axpy_row2_lens_bwd_acc2(const float* g, const float* alpha, const float* gm, const float* act,
+                                 const float* s1, const float* s2, const float* y, float* dy, float* ds1, float* ds2,
+                                 float* dx, const int32_t* lens, int64_t B, int64_t L, int64_t d,
+                                 asrx_stream_t stream);
+/* asrx_msheath_dx_final taking dpooled (B, d) itself: dx += (has_orig[b] ? dorig : 0) + dpooled[b, :] (1 / T_b) on live
+ * rows, the product rounded as asrx_lincomb stores it; pad rows of dx are zeros and dorig is not read there */
+int asrx_msheath_lens_dx_final(float* dx, const float* dorig, const int* has_orig, const float* dpooled,
+                               const int32_t* lens, int64_t B, int64_t L, int64_t d, asrx_stream_t stream);
+/* asrx_row_tiles listing a tile only if it holds a live row of a sample at the layer (next_i may be null: all are) */
+int asrx_row_lens_tiles(const float* next_i, int64_t layer, const int32_t* lens, int64_t L, int64_t M, int* mtiles,
+                        int* n_mtiles, asrx_stream_t stream);
 int asrx_stem1_fwd(const float* x, const float* W, const float* bias, float* y, int64_t B, int64_t T, int64_t D,
                    asrx_stream_t stream);
 int asrx_stem1_bwd(const float* g, const float* x, float* dW, float* db, int64_t B, int64_t T, int64_t D,
